@@ -17,11 +17,17 @@ step).  `value` = data symbols demodulated by all ranks / max-over-ranks time.
 `--gpus N` without WORLD_SIZE starts the N ranks itself (one process per
 GPU); under torch.distributed.run it checks WORLD_SIZE == N.
 
-Also reported: the high-level lora_phy::demodulate path (mode A), the
-dominant kernel's roofline fraction (HIP events on the launch stream), and
-the reference CPU path timed on this host's cores (rank 0, N = 1).
+A plain run sets up, warms up, times the K steps and prints the result line
+(with the dominant kernel's roofline fraction, from HIP events recorded
+inside the timed steps).  `--dump-outputs DIR` also writes what the last
+timed step computed as DIR/*.npy (dump_outputs).  `--full` adds everything
+that takes runs or CPU work of its own: the payload / oracle checks, the
+per-stage kernel times, the high-level lora_phy::demodulate path (mode A),
+the PMC traffic lookup, `--sweep` / `--csv`, and the reference CPU path
+timed on this host's cores (rank 0, N = 1).
 
 Run: python bench.py [--gpus N --steps K --warmup W --sf 7 --frames F]
+                     [--dump-outputs DIR] [--full]
 """
 from __future__ import annotations
 
@@ -68,6 +74,11 @@ def parse():
     ap.add_argument("--sf", type=int, default=7)
     ap.add_argument("--bw", type=int, default=125000)
     ap.add_argument("--frames", type=int, default=0, help="frames per GPU (0 = config default)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the checks, stage times, mode A, --sweep / --csv and the CPU baseline "
+                         "(off: only the timed steps and the result line)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's results as DIR/<name>.npy (c1 / c2)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--no-mode-a", action="store_true")
@@ -81,7 +92,12 @@ def parse():
     ap.add_argument("--total-frames", type=int, default=0,
                     help="c3: frames over all ranks (default 131072 per rank: the 1 M frames of "
                          "C3 on 8 GPUs, ~93 GB of IQ resident per GPU)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if (args.sweep or args.csv) and not args.full:
+        ap.error("--sweep and --csv are part of the --full run: add --full")
+    if args.dump_outputs and args.config in ("c3", "c4"):
+        ap.error("--dump-outputs covers the c1 / c2 configurations")
+    return args
 
 
 class Workload:
@@ -274,6 +290,45 @@ def timed(wl: Workload, mode: int, steps: int, warmup: int, world: int, events: 
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
     return dt
+
+
+DUMP_BYTES = 64_000_000  # --dump-outputs writes at most this much
+
+
+def dump_outputs(path: str, parts: list) -> dict:
+    """What a caller of the timed path holds after the last timed step, as
+    .npy files under `path`: per rank in `parts` the (uint16 symbols [n, 64],
+    uint8 payloads [n, 32], 32-byte frame records [n, 32]) it received,
+    ranks concatenated in order.
+
+      symbols.npy   float32 [n, 64]  demodulated data symbols
+      payloads.npy  float32 [n, 32]  decoded payload bytes
+      records.npy   float64 [n, 12]  the frame records' fields, in
+                                     lphy.META_DTYPE's order (cfo, time_offset,
+                                     rate, scale, t_off, status, sw0, sw1,
+                                     sync_word, crc_ok, normalised, have_sync)
+
+    Above DUMP_BYTES in all, a fixed seeded sample of the frames is written
+    instead (ascending), with its indices in frames.npy (float64 [n])."""
+    syms = np.concatenate([p[0] for p in parts])
+    pay = np.concatenate([p[1] for p in parts])
+    rec = np.ascontiguousarray(np.concatenate([p[2] for p in parts])).reshape(-1).view(lphy.META_DTYPE)
+    n = syms.shape[0]
+    per_frame = 4 * syms.shape[1] + 4 * pay.shape[1] + 8 * len(lphy.META_DTYPE.names) + 8
+    keep = DUMP_BYTES // per_frame
+    out = Path(path)
+    out.mkdir(parents=True, exist_ok=True)
+    if n > keep:
+        idx = np.sort(np.random.default_rng(0xD0).choice(n, keep, replace=False))
+        syms, pay, rec = syms[idx], pay[idx], rec[idx]
+        np.save(out / "frames.npy", idx.astype(np.float64))
+    else:
+        (out / "frames.npy").unlink(missing_ok=True)
+    np.save(out / "symbols.npy", syms.astype(np.float32))
+    np.save(out / "payloads.npy", pay.astype(np.float32))
+    np.save(out / "records.npy",
+            np.stack([rec[k].astype(np.float64) for k in lphy.META_DTYPE.names], axis=1))
+    return {"dir": str(out), "frames": int(syms.shape[0]), "of": int(n)}
 
 
 def rank_payloads(sf: int, frames: int, rank: int) -> np.ndarray:
@@ -752,8 +807,20 @@ def main():
     live_ev: list = []
     dt = timed(wl, mode_b, args.steps, args.warmup, world, events=live_ev, settle_s=SETTLE_S, gat=gat)
     gathered = None
-    if gat:
-        parts = gat.finish()
+    parts = gat.finish() if gat else None
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the last timed step's results, before anything else runs: rank 0's
+        # gathered slabs (N > 1), or this rank's own output set
+        if gat:
+            res = [shard.unpack_slab(parts[r], [frames], DATA_SYMS, PAYLOAD)[0] for r in range(world)]
+        else:
+            torch.cuda.synchronize()
+            res = [(wl.syms.cpu().numpy().view(np.uint16).reshape(frames, DATA_SYMS),
+                    wl.pay.cpu().numpy().reshape(frames, PAYLOAD),
+                    wl.meta.cpu().numpy().reshape(frames, 32))]
+        dumped = dump_outputs(args.dump_outputs, res)
+    if gat and args.full:
         if rank == 0:
             gathered = check_gathered(parts, args.sf, frames, world)
         wl.run(mode_b)  # slot 0 holds the results the local checks read
@@ -761,8 +828,10 @@ def main():
     live_kernel_ms = float(np.mean([a.elapsed_time(b) for a, b in live_ev]))
     data_syms = world * frames * DATA_SYMS
     value = data_syms * args.steps / dt
-    check_b = wl.check(mode_b)
-    st = wl.stage_times(mode_b)
+    fused = frames_fused(args.sf)
+    # (--full only, and every step below it: runs and CPU work of their own)
+    check_b = wl.check(mode_b) if args.full else None
+    st = wl.stage_times(mode_b) if args.full or not fused else None
 
     N = wl.N
     # dominant kernel = the fused launch (k_wave from SF 7, k_frames below):
@@ -770,17 +839,17 @@ def main():
     # symbol + the 32-B frame record (the two-symbol scans and the
     # settled frames' estimate re-reads are extra traffic, which the PMC
     # summary below shows)
-    fused = frames_fused(args.sf)
     kern_bytes = frames * (wl.fs * 8 + DATA_SYMS * 2 + (32 if fused else 0))
     # the fused launch timed live in the timed region (k_wave + its fix-up
     # launch, which is empty unless a frame needs the exact re-run)
     kern_ms = live_kernel_ms if fused else st["unfused_symbols"]
     achieved = kern_bytes / (kern_ms * 1e-3) / 1e9
     step_gbps = frames * DATA_SYMS * bytes_per_data_symbol(N) / (ms * 1e-3) / 1e9
-    traffic = measured_traffic(fused_kernel(args.sf) if fused else f"k_demod<{args.sf}>", frames)
+    traffic = (measured_traffic(fused_kernel(args.sf) if fused else f"k_demod<{args.sf}>", frames)
+               if args.full else None)
 
     extra = {}
-    if not args.no_mode_a:
+    if args.full and not args.no_mode_a:
         # (the same warmup as the headline's W steps: mode A's kernels are
         # other code objects, and the first launches after a change of
         # kernel run at the transient clocks §4.3 of DESIGN describes)
@@ -807,7 +876,7 @@ def main():
             write_perf_csv(args.csv, args.run_id, [head] + rows)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline(wl, args.cpu_seconds)
         except Exception as e:
@@ -853,6 +922,11 @@ def main():
             "cpu_baseline": cpu,
         }
         line.update(extra)
+        if not args.full:  # the plain line carries only what the timed steps gave
+            for k in ("stage_ms", "check", "gathered_rank0", "cpu_baseline"):
+                del line[k]
+        if dumped:
+            line["dumped_outputs"] = dumped
         if REHEARSE:
             line["rehearsal"] = "all ranks on cuda:0 over gloo (LPHY_BENCH_REHEARSE): not a scaling result"
         print(json.dumps(line))

@@ -72,8 +72,20 @@ def workdir(tmp_path):
     return tmp_path
 
 
-def _run(exe, cwd, timeout=300, **kw):
-    return subprocess.run([str(exe)], cwd=cwd, capture_output=True, text=True, timeout=timeout, **kw)
+PKGLIB = ROOT / "lora-sdr-lightweight-standalone-library-clean_amd" / "lib"
+
+
+def _env(libdir=PKGLIB, **extra):
+    """The environment of a harness executable: the drop-in's libraries are
+    taken from this tree's lib/ (or lib/san), wherever oracle/_ref was built
+    (its executables' own run path is relative to them, oracle/Makefile)."""
+    path = os.pathsep.join(p for p in (str(libdir), os.environ.get("LD_LIBRARY_PATH", "")) if p)
+    return dict(os.environ, LD_LIBRARY_PATH=path, **extra)
+
+
+def _run(exe, cwd, timeout=300, env=None):
+    return subprocess.run([str(exe)], cwd=cwd, capture_output=True, text=True, timeout=timeout,
+                          env=env or _env())
 
 
 LIBS = ("liblphy_hip.so", "liblora_phy_amd.so")
@@ -134,7 +146,7 @@ def test_lora_phy_tests_binary(workdir):
     out = {}
     for side in ("amd", "ref"):
         trace = workdir / f"trace_{side}.txt"
-        p = _run(H / side / "lora_phy_tests", workdir, env=dict(os.environ, LPHY_CRASH_TRACE=str(trace)))
+        p = _run(H / side / "lora_phy_tests", workdir, env=_env(LPHY_CRASH_TRACE=str(trace)))
         out[side] = (p, trace.read_text() if trace.exists() else "")
     ours, ref = out["amd"][0], out["ref"][0]
     assert ref.returncode < 0, (ref.returncode, ref.stderr[-2000:])
@@ -153,7 +165,7 @@ def test_sync_word_fault_pinned(workdir):
     code called from sync_word_test_main, never in the drop-in's libraries."""
     for side in ("amd", "ref"):
         trace = workdir / f"trace_sw_{side}.txt"
-        p = _run(H / side / "sync_word_test", workdir, env=dict(os.environ, LPHY_CRASH_TRACE=str(trace)))
+        p = _run(H / side / "sync_word_test", workdir, env=_env(LPHY_CRASH_TRACE=str(trace)))
         if side == "ref":
             assert p.returncode < 0, p.stderr[-2000:]
         if p.returncode < 0:
@@ -174,7 +186,8 @@ def test_sync_word_overflow_under_asan(workdir):
     no other memory error; and the test then reaches the same verdict in
     both builds."""
     rc = {}
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:protect_shadow_gap=0:halt_on_error=0:symbolize=1")
+    env = _env(PKGLIB / "san",
+               ASAN_OPTIONS="detect_leaks=0:protect_shadow_gap=0:halt_on_error=0:symbolize=1")
     for side in ("amd", "ref"):
         exe = H / "asan" / side / "sync_word_test"
         if not exe.exists():
@@ -201,10 +214,10 @@ def test_tx_rx_runner_pipe(workdir, payload, sf):
     out = {}
     for side in ("amd", "ref"):
         tx = subprocess.run([str(H / side / "tx_runner"), f"--payload={payload}", f"--sf={sf}", "--stdout"],
-                            cwd=workdir, capture_output=True, timeout=120)
+                            cwd=workdir, capture_output=True, timeout=120, env=_env())
         assert tx.returncode == 0, tx.stderr
         rx = subprocess.run([str(H / side / "rx_runner"), f"--sf={sf}", "--report-offsets"], input=tx.stdout,
-                            cwd=workdir, capture_output=True, timeout=120)
+                            cwd=workdir, capture_output=True, timeout=120, env=_env())
         assert rx.returncode == 0, rx.stderr
         out[side] = (tx.stdout, rx.stdout.decode())
     assert out["amd"][0] == out["ref"][0]  # the IQ, byte for byte

@@ -6,7 +6,7 @@
 # Output: <outdir>/<pass>/run_counter_collection.csv
 set -u
 OUT=$1; shift
-ARGS=${*:-"--steps 2 --warmup 1 --no-cpu-baseline --no-mode-a"}
+ARGS=${*:-"--full --steps 2 --warmup 1 --no-cpu-baseline --no-mode-a"}
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp && export TMPDIR=/tmp
 mkdir -p "$ROOT/$OUT"

@@ -4,7 +4,7 @@
 #   tools/pmc_fw.sh <outdir> [bench args]      (GPU box, repo root)
 set -u
 OUT=$1; shift
-ARGS=${*:-"--config c2 --steps 2 --warmup 1 --no-cpu-baseline --no-mode-a"}
+ARGS=${*:-"--full --config c2 --steps 2 --warmup 1 --no-cpu-baseline --no-mode-a"}
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp && export TMPDIR=/tmp
 mkdir -p "$ROOT/$OUT"
