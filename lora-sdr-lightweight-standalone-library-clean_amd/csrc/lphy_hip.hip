@@ -1,39 +1,23 @@
-// lphy_hip.hip — MI355X (gfx950) LoRa PHY demodulation kernels + C ABI.
-//
-// Hot path: per frame a prologue (whole-frame max|I|,|Q| for
-// lora_demodulate's normalisation, LoRaDemod.cpp:60-78, and the two-symbol
-// CFO/timing estimate, LoRaDemod.cpp:80-136 / phy.cpp:81-148), then per
-// symbol CFO rotation -> KISS-identical FFT -> |X|^2 argmax
-// (LoRaDemod.cpp:142-176 / phy.cpp:204-238), then per frame Hamming(8,4)
-// decode + sx1272 CRC (LoRaDecoder.cpp:7-21, phy.cpp:245-261).
-//
-// Kernels:
-//   k_prologue   one 256-thread workgroup per frame: max-abs reduction,
-//                estimate FFTs (tile machinery of lphy_fft.h), offsets.
-//   k_demod<SF>  256-thread tiles of T = 256/(N/16) symbols; each symbol is
-//                staged to LDS with coalesced cf32 loads while the rotation
-//                (glibc-exact sincosf in FP64) is applied, transformed by
-//                LPS = N/16 lanes holding 16 complex each, and reduced by
-//                cross-lane argmax.  No MFMA: the path is HBM/VALU bound.
-//   k_finalize   one thread per frame: sync word, decode, CRC.
-//   k_modulate*  bit-exact lora_modulate (producer for synthetic IQ).
-//
-// All device arithmetic is built with -ffp-contract=off (see
-// __graft_entry__.build); every product/sum is evaluated in the reference's
-// operand order so that symbol indices, sync words and decoded bytes are
-// bit-identical to the reference's CPU path.
-#include "lphy_kernels.h"
+// lphy_hip.hip — the C ABI (include/lphy_hip.h) of the MI355X (gfx950) LoRa
+// PHY library: contexts and their constant tables, the per-call choice of
+// kernels (lphy_route.h) and their launch through the per-SF tables (SfOps:
+// the kernels templated on SF are the lphy_sf.hip objects'), and the
+// SF-independent kernels themselves: the finalisation (k_finalize), the
+// modulator and the compensation (lphy_mod.h), k_mark_recheck.
+#include "lphy_args.h"
+#include "lphy_final.h"
+#include "lphy_mod.h"
+#include "lphy_route.h"
 #include "lphy_testing.h"
 
+#include <cmath>
+#include <complex>
 #include <cstring>
 #include <memory>
 #include <atomic>
 #include <mutex>
 #include <vector>
 
-// ===========================================================================
-// Host side
-// ===========================================================================
 #ifndef __HIP_DEVICE_COMPILE__
 // Empty launch tables, overridden by every lphy_sf.hip object linked in
 // (experiment builds may link only the SF they time: tools/ubench/variants.py)
@@ -106,18 +90,7 @@ struct lphy_hip_ctx {
     // calls on different streams or threads of one context never share it)
 };
 
-
 namespace {
-
-#define HIP_OK(x)                                                         \
-    do {                                                                  \
-        hipError_t e_ = (x);                                              \
-        if (e_ != hipSuccess) {                                           \
-            fprintf(stderr, "lphy_hip: %s failed: %s (%s:%d)\n", #x,      \
-                    hipGetErrorString(e_), __FILE__, __LINE__);           \
-            return -EIO;                                                  \
-        }                                                                 \
-    } while (0)
 
 // Host-side constant tables with the reference's own libm calls.
 void make_twiddles(std::vector<std::complex<float>>& tw, int nfft) {
@@ -152,36 +125,6 @@ void make_hann(std::vector<float>& w, int N) {
                                       (static_cast<float>(N) - 1.0f));
 }
 
-// Whether k_frames can take this batch: a symbol within one wavefront, the
-// two-symbol estimate, and frames long enough that a frame's estimate tile
-// precedes its first symbol tile by two tiles (S + 3 >= 2 * units/tile).
-inline bool frames_fit(unsigned sf, unsigned osr, int est_units, size_t total) {
-    if (sf > 10 || osr != 1 || est_units != 2 || total < 2) return false;
-    const size_t E = sf >= 4 ? 16 : ((size_t)1 << sf);
-    const size_t lps = ((size_t)1 << sf) / E;
-    const size_t wt = 64 / lps;
-    return total + 1 >= 2 * wt;
-}
-
-// Whether the fused kernel k_wave (64 x 64 values per wavefront unit)
-// takes this batch: SF 7-12, osr 1, the two-symbol estimate, the certified
-// rotation, in modes 1/2 the speculative normalisation, and below SF 9 at
-// least one unit of symbols per frame (4096 / N: its units span frames
-// there); with or without the Hann window (round 6: its N floats beside the
-// down-chirp in LDS; SF 12 with three waves per workgroup, wave_wpb, and not
-// in mode 1, whose windowed k_wave spilled).
-// LPHY_F_EXACT_ROTATION, the pre-scan schedule and shorter frames stay on
-// k_frames (SF <= 10) or the separate launches (SF 11-12).
-#ifndef LPHY_WAVE_MIN_SF  // smallest SF on k_wave (-D for timing experiments only)
-#define LPHY_WAVE_MIN_SF 7
-#endif
-inline bool wave_fit(unsigned sf, unsigned osr, int est_units, size_t total, int mode, const DemodArgs& A) {
-    return sf >= LPHY_WAVE_MIN_SF && sf <= 12 && (sf >= 9 || total >= (size_t)(4096u >> sf)) && osr == 1 &&
-           !(sf == 12 && A.win && mode == LPHY_MODE_LORA_DEMODULATE) && est_units == 2 && total >= 2 &&
-           !A.exact_rotation &&
-           (mode == LPHY_MODE_DEMODULATE || A.spec);
-}
-
 const SfOps* sf_ops(unsigned sf) {
     static const SfOps* const t[13] = {nullptr,    &sf_ops_1, &sf_ops_2, &sf_ops_3,  &sf_ops_4,
                                        &sf_ops_5,  &sf_ops_6, &sf_ops_7, &sf_ops_8,  &sf_ops_9,
@@ -189,22 +132,37 @@ const SfOps* sf_ops(unsigned sf) {
     return sf >= 1 && sf <= 12 && t[sf]->demod ? t[sf] : nullptr;
 }
 
-int launch_demod(unsigned sf, const DemodArgs& A, hipStream_t st, bool pro, bool sym, int per_cu = 0) {
-    const SfOps* o = sf_ops(sf);
-    return o ? o->demod(A, st, pro, sym, per_cu) : -EINVAL;
+// LPHY_F_DEBUG_RECHECK (tests): every frame the prologue estimated (status
+// 0) is marked as if another workgroup had already left a sentinel in it, the
+// state a symbol of the separate launches may observe at any time
+// (sym_ctx); k_post's recheck then finds no sentinel and clears the mark.
+__global__ void k_mark_recheck(lphy_frame_meta* meta, unsigned long long frames) {
+    const unsigned long long f = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (f < frames && meta[f].status == 0) meta[f].status = kStatusRecheck;
 }
 
-int launch_frames(unsigned sf, const DemodArgs& A, hipStream_t st) {
-    const SfOps* o = sf_ops(sf);
-    return o ? o->frames(A, st) : -ENOTSUP;
+// lphy_hip_decode_batch: the finalisation alone (k_post runs it after the
+// re-runs of a demodulation), a workgroup per 256 frames
+__global__ __launch_bounds__(kTile) void k_finalize(FinalArgs A) {
+    __shared__ FinStage st;
+#ifndef LPHY_AB_FINAL_THREAD  // A/B timing only: a row per thread straight from memory
+    if (blockDim.x == kTile && finalize_block(A, (unsigned long long)blockIdx.x * kTile, st)) return;
+#endif
+    const unsigned long long f = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (f < A.frames) finalize_frame(A, f);
 }
 
-int launch_post(unsigned sf, int mode, const DemodArgs& A, const FinalArgs& F, bool fix, bool fin,
-                hipStream_t st) {
-    const SfOps* o = sf_ops(sf);
-    return o ? o->post(mode, A, F, fix, fin, st) : -EINVAL;
+// The separate launches: prologue and / or symbols.  Under
+// LPHY_F_DEBUG_RECHECK the mark goes between the two, on the same stream.
+int launch_demod(const SfOps* o, const DemodArgs& A, hipStream_t st, bool pro, bool sym) {
+    if (!(A.debug_recheck && sym)) return o->demod(A, st, pro, sym, 0);
+    if (pro) {
+        if (int rc = o->demod(A, st, true, false, 0)) return rc;
+    }
+    hipLaunchKernelGGL(k_mark_recheck, dim3((unsigned)((A.frames + kTile - 1) / kTile)), dim3(kTile), 0, st, A.meta,
+                       A.frames);
+    return o->demod(A, st, false, true, 0);
 }
-
 
 // Smallest batch the fused kernels take.  They give each frame one
 // wavefront that walks its symbols in order, so a small batch leaves most
@@ -287,7 +245,6 @@ struct StreamScratch {
         }
     }
 };
-
 
 }  // namespace
 
@@ -507,19 +464,18 @@ int demod_batch_impl(lphy_hip_ctx* c, const float* d_iq, size_t frames, size_t f
         return -ERANGE;
     const unsigned stages = flags & (LPHY_F_STAGE_PROLOGUE | LPHY_F_STAGE_SYMBOLS | LPHY_F_STAGE_FINAL);
     const bool all = stages == 0;
-    // one fused launch for prologue + symbols when the frame shape allows it
-    // (see k_frames); selecting exactly those two stages runs it alone
+    // one fused launch for prologue + symbols when the call's shape allows it
+    // (lphy_route.h); selecting exactly those two stages runs it alone
     const unsigned both = LPHY_F_STAGE_PROLOGUE | LPHY_F_STAGE_SYMBOLS;
     // (Measured alternative: the separate kernels pipelined over chunks on
     // two streams, prologue of chunk c+1 beside the symbol kernel of chunk
     // c: the co-running kernels slowed each other ~2x, 1.1x slower overall.)
-    // (LPHY_F_FRAMES_KERNEL, test build: k_frames where k_wave would run -
-    // SF 7-10; the certificate tests on k_frames)
-    const bool wfit = wave_fit(c->sf, c->osr, A.est_units, total, mode, A) &&
-                      !(flags & LPHY_F_FRAMES_KERNEL);
-    const bool fused = (all || (stages & both) == both) && !(flags & LPHY_F_UNFUSED) &&
-                       frames >= fused_min_frames(c) && (frames_fit(c->sf, c->osr, A.est_units, total) || wfit);
-    A.wave = fused && (c->sf >= 11 || wfit) ? 1 : 0;
+    const Path path = route({c->sf, c->osr, mode, A.win != nullptr, total, A.est_units, frames, fused_min_frames(c),
+                             A.spec != 0, A.exact_rotation != 0, flags});
+    const bool fused = path != Path::Separate;
+    A.wave = path == Path::Wave ? 1 : 0;
+    const SfOps* ops = sf_ops(c->sf);
+    if (!ops) return fused ? -ENOTSUP : -EINVAL;  // (an experiment build without this SF's object)
     // SF 11-12 separate launches, modes 1/2: the speculative normalisation
     // of k_frames across workgroups (k_maxabs scans the two estimate
     // symbols, k_demod folds the rest, k_post closes each frame); needs the
@@ -532,9 +488,10 @@ int demod_batch_impl(lphy_hip_ctx* c, const float* d_iq, size_t frames, size_t f
         if (int rc = spec.get(frames * sizeof(uint4))) return rc;
         A.spec_big = static_cast<uint4*>(spec.p);
     }
-    int rc = fused ? launch_frames(c->sf, A, st)
-                   : launch_demod(c->sf, A, st, all || (stages & LPHY_F_STAGE_PROLOGUE),
-                                  all || (stages & LPHY_F_STAGE_SYMBOLS));
+    int rc = path == Path::Wave     ? ops->wave(A, st)
+             : path == Path::Frames ? ops->frames(A, st)
+                                    : launch_demod(ops, A, st, all || (stages & LPHY_F_STAGE_PROLOGUE),
+                                                   all || (stages & LPHY_F_STAGE_SYMBOLS));
     if (rc) return rc;
     // exact re-run of flagged frames (part of the symbols stage) and the
     // per-frame finalisation, in one launch
@@ -551,7 +508,7 @@ int demod_batch_impl(lphy_hip_ctx* c, const float* d_iq, size_t frames, size_t f
     F.shift = c->sf > 4 ? (int)c->sf - 4 : 0;
     F.decode = (flags & LPHY_F_DECODE) ? 1 : 0;
     F.set_sync = 1;
-    return launch_post(c->sf, mode, A, F, fix, fin, st);
+    return ops->post(mode, A, F, fix, fin, st);
 }
 }  // namespace
 

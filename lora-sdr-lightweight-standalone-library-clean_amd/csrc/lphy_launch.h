@@ -1,0 +1,206 @@
+// lphy_launch.h — the host launch templates of one spreading factor, the
+// entries of its SfOps table (lphy_sf.hip, the only includer).  Which of
+// them a call takes is lphy_route.h's decision (lphy_hip.hip); which kernels
+// exist here follows the same header's frames_kernel / wave_kernel, so a
+// routed call always finds its kernel and the -ENOTSUP returns below only
+// guard a table entry that does not exist.
+#pragma once
+#include <type_traits>
+
+#include "lphy_demod.h"
+#include "lphy_frames.h"
+#include "lphy_post.h"
+#include "lphy_route.h"
+#include "lphy_wave.h"
+
+namespace {
+
+// The kernels' compile-time MODE of a call: the lphy_mode, kWinBit with a
+// window (WIN: the kernel family has windowed forms), kOsrBit with osr > 1
+// (OSR: ... oversampled forms).  Calls fn(std::integral_constant<int, MODE>).
+template <int BITS, class Fn>
+int with_mode_bits(int mode, Fn&& fn) {
+    switch (mode) {
+        case LPHY_MODE_DEMODULATE: return fn(std::integral_constant<int, LPHY_MODE_DEMODULATE | BITS>{});
+        case LPHY_MODE_LORA_DEMODULATE: return fn(std::integral_constant<int, LPHY_MODE_LORA_DEMODULATE | BITS>{});
+        default: return fn(std::integral_constant<int, LPHY_MODE_DECHIRP_LORA_DEMODULATE | BITS>{});
+    }
+}
+template <bool WIN, bool OSR, class Fn>
+int with_mode(int mode, bool win, bool osr, Fn&& fn) {
+    if constexpr (OSR) {
+        if (osr) return win ? with_mode_bits<kWinBit | kOsrBit>(mode, fn) : with_mode_bits<kOsrBit>(mode, fn);
+    }
+    if constexpr (WIN) {
+        if (win) return with_mode_bits<kWinBit>(mode, fn);
+    }
+    return with_mode_bits<0>(mode, fn);
+}
+
+// CUs of the device (queried once) ...
+inline int cu_count() {
+    static const int cus = [] {
+        int dev = 0, n = 0;
+        (void)hipGetDevice(&dev);
+        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+        return n > 0 ? n : 256;
+    }();
+    return cus;
+}
+// ... and the persistent grid of kernel K: every workgroup of kTile threads
+// the device holds at once
+template <auto K>
+int resident_grid() {
+    static const int grid = [] {
+        int per = 0;
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, K, kTile, 0);
+        return cu_count() * (per > 0 ? per : 1);
+    }();
+    return grid;
+}
+
+// Waves per SIMD the demod kernel is register-budgeted for (launch bound):
+// 3 (<= 168 VGPRs) or 2 (<= 256; the oversampled forms).
+constexpr int demod_occ(int sf) { return sf <= 8 ? 3 : 2; }
+
+// per_cu > 0 caps the persistent grid at per_cu workgroups per CU (room
+// for a concurrent kernel on another stream)
+template <int SF, int MODE, int OCC>
+void launch_symbols(const DemodArgs& A0, hipStream_t st, int per_cu) {
+    using G = Geo<SF>;
+    constexpr bool WAVE = G::LPS <= 64;
+    constexpr int WT = WAVE ? 64 / G::LPS : G::T;      // symbols per worker tile
+    constexpr int WPB = WAVE ? kTile / 64 : 1;         // workers per workgroup
+    unsigned long long g = (unsigned long long)resident_grid<&k_demod<SF, MODE, OCC>>();
+    if (per_cu > 0 && g > (unsigned long long)per_cu * cu_count()) g = (unsigned long long)per_cu * cu_count();
+    const unsigned long long wtiles = (A0.frames * A0.total_syms + WT - 1) / WT;
+    unsigned long long grid = (wtiles + WPB - 1) / WPB;
+    if (grid > g) grid = g;
+    DemodArgs A = A0;
+    const unsigned long long stride = grid * WPB * WT;  // symbols per worker step
+    A.stride_f = (unsigned)(stride / A0.total_syms);
+    A.stride_s = (unsigned)(stride % A0.total_syms);
+    hipLaunchKernelGGL((k_demod<SF, MODE, OCC>), dim3((unsigned)grid), dim3(kTile), 0, st, A);
+}
+
+// The separate launches: prologue (k_maxabs in modes 1/2, k_estimate) and /
+// or the symbols (k_demod).
+template <int SF>
+int launch_demod_sf(const DemodArgs& A, hipStream_t st, bool prologue, bool symbols, int per_cu) {
+    using G = Geo<SF>;
+    if (prologue) {
+        if (A.mode != LPHY_MODE_DEMODULATE)
+            hipLaunchKernelGGL(k_maxabs<SF>, dim3((unsigned)A.frames), dim3(kTile), 0, st, A);
+        const int fpt = A.est_units <= G::T ? G::T / A.est_units : 1;
+        const unsigned long long blocks = (A.frames + fpt - 1) / fpt;
+        hipLaunchKernelGGL(k_estimate<SF>, dim3((unsigned)blocks), dim3(kTile), 0, st, A);
+    }
+    if (symbols && A.frames * A.total_syms) {
+        with_mode<true, true>(A.mode, A.win != nullptr, A.osr > 1, [&](auto m) {
+            constexpr int MODE = decltype(m)::value;
+            if constexpr (!(MODE & kOsrBit)) {
+                launch_symbols<SF, MODE, demod_occ(SF)>(A, st, per_cu);
+            } else if constexpr ((MODE & 3) != LPHY_MODE_DECHIRP_LORA_DEMODULATE) {
+                // oversampled input: strided symbol loads (no dechirp mode here)
+                launch_symbols<SF, MODE, 2>(A, st, per_cu);
+            }
+            return 0;
+        });
+    }
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// Waves per SIMD of k_frames: 2 (<= 256 VGPRs; its loop carries more state
+// than k_demod's and spills at 3).
+#ifndef LPHY_FRAMES_OCC  // experiments: -DLPHY_FRAMES_OCC=3
+#define LPHY_FRAMES_OCC 2
+#endif
+// Fused path, k_frames (lphy_frames.h).
+template <int SF>
+int launch_frames_sf(const DemodArgs& A, hipStream_t st) {
+    static_assert(Geo<SF>::LPS == lphy::route_lps(SF), "lphy_route.h's table: Geo<SF>::LPS");
+    if constexpr (!lphy::frames_kernel(SF)) {
+        (void)A; (void)st;
+        return -ENOTSUP;
+    } else {
+        return with_mode<true, false>(A.mode, A.win != nullptr, false, [&](auto m) {
+            constexpr int MODE = decltype(m)::value;
+            FrameArgs P{};
+            P.A = A;
+            constexpr unsigned WPB = kTile / 64;
+            unsigned long long blocks = (unsigned long long)resident_grid<&k_frames<SF, MODE, LPHY_FRAMES_OCC>>();
+            const unsigned long long need = (A.frames + WPB - 1) / WPB;
+            if (blocks > need) blocks = need;
+            P.waves = (unsigned)(blocks * WPB);
+            hipLaunchKernelGGL((k_frames<SF, MODE, LPHY_FRAMES_OCC>), dim3((unsigned)blocks), dim3(kTile), 0, st, P);
+            HIP_OK(hipGetLastError());
+            return 0;
+        });
+    }
+}
+
+// Fused wave-per-symbol path, SF 7-12: k_wave (lphy_wave.h): one wave per
+// SIMD, 256-thread workgroups (wave_wpb), the next unit staged through LDS
+// by DMA while a unit computes; its units span frames where lphy_route.h's
+// wave_spans says so.
+template <int SF>
+int launch_wave_sf(const DemodArgs& A, hipStream_t st) {
+    if constexpr (lphy::route_spw(SF) == 0) {
+        (void)A; (void)st;
+        return -ENOTSUP;
+    } else {
+        static_assert(WGeo<SF>::SPW == lphy::route_spw(SF), "lphy_route.h's table: WGeo<SF>::SPW");
+        return with_mode<true, false>(A.mode, A.win != nullptr, false, [&](auto m) {
+            constexpr int MODE = decltype(m)::value;
+            constexpr bool WIN = (MODE & kWinBit) != 0;
+            FrameArgs P{};
+            P.A = A;
+            constexpr int WPB = wave_wpb<SF, MODE>();
+            unsigned long long blocks = (unsigned long long)cu_count();
+            const unsigned long long need = (A.frames + WPB - 1) / WPB;
+            if (blocks > need) blocks = need;
+            P.waves = (unsigned)(blocks * WPB);
+            if constexpr (lphy::wave_kernel(SF, MODE & 3, WIN, true)) {
+                if (lphy::wave_spans(SF, A.total_syms)) {
+                    hipLaunchKernelGGL((k_wave<SF, MODE, true>), dim3((unsigned)blocks), dim3(64 * WPB), 0, st, P);
+                    HIP_OK(hipGetLastError());
+                    return 0;
+                }
+            }
+            if constexpr (lphy::wave_kernel(SF, MODE & 3, WIN, false)) {
+                hipLaunchKernelGGL((k_wave<SF, MODE, false>), dim3((unsigned)blocks), dim3(64 * WPB), 0, st, P);
+                HIP_OK(hipGetLastError());
+                return 0;
+            } else {
+                return -ENOTSUP;
+            }
+        });
+    }
+}
+
+// After the symbol kernels: k_spec_settle where the separate launches
+// speculated (A.spec_big: SF 11-12, modes 1/2), then k_post.
+template <int SF>
+int launch_post_sf(int mode, const DemodArgs& A, const FinalArgs& F, bool fix, bool fin, hipStream_t st) {
+    return with_mode<false, false>(mode, false, false, [&](auto m) {
+        constexpr int MODE = decltype(m)::value;
+        if constexpr (MODE != LPHY_MODE_DEMODULATE) {
+            if (fix && A.spec_big)
+                hipLaunchKernelGGL((k_spec_settle<SF, MODE>), dim3((unsigned)A.frames), dim3(kTile), 0, st, A);
+        }
+        hipLaunchKernelGGL((k_post<SF, MODE>), dim3((unsigned)((A.frames + kTile - 1) / kTile)), dim3(kTile), 0, st, A,
+                           F, (int)fix, (int)fin);
+        HIP_OK(hipGetLastError());
+        return 0;
+    });
+}
+
+template <int SF>
+int launch_estimate_sf(const DemodArgs& A, hipStream_t st) {
+    const int fpt = A.est_units <= Geo<SF>::T ? Geo<SF>::T / A.est_units : 1;
+    hipLaunchKernelGGL(k_estimate<SF>, dim3((unsigned)((A.frames + fpt - 1) / fpt)), dim3(kTile), 0, st, A);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+}  // namespace

@@ -1,6 +1,7 @@
 // lphy_sf.hip — the kernels of one spreading factor (built once per SF with
-// -DLPHY_SF=n, see ../Makefile) and their launch table for lphy_hip.hip.
-#include "lphy_kernels.h"
+// -DLPHY_SF=n, see ../Makefile) and their launch table for lphy_hip.hip,
+// which holds the SF-independent kernels itself.
+#include "lphy_launch.h"
 
 #ifndef LPHY_SF
 #error "build with -DLPHY_SF=<1..12>"
@@ -13,6 +14,7 @@
 namespace {
 template int launch_demod_sf<LPHY_SF>(const DemodArgs&, hipStream_t, bool, bool, int);
 template int launch_frames_sf<LPHY_SF>(const DemodArgs&, hipStream_t);
+template int launch_wave_sf<LPHY_SF>(const DemodArgs&, hipStream_t);
 template int launch_post_sf<LPHY_SF>(int, const DemodArgs&, const FinalArgs&, bool, bool, hipStream_t);
 template int launch_estimate_sf<LPHY_SF>(const DemodArgs&, hipStream_t);
 }  // namespace
@@ -38,6 +40,7 @@ namespace lphy {
 const SfOps LPHY_CAT(sf_ops_, LPHY_SF) = {
     &launch_demod_sf<LPHY_SF>,
     &launch_frames_sf<LPHY_SF>,
+    &launch_wave_sf<LPHY_SF>,
     &launch_post_sf<LPHY_SF>,
     &launch_estimate_sf<LPHY_SF>,
 #ifdef LPHY_DEBUG_BOUNDS

@@ -34,7 +34,7 @@ enum lphy_test_flags {
                                    // kernels: every symbol left to k_post's
                                    // exact re-run (tests/test_gpu_concurrency.py)
     LPHY_F_FRAMES_KERNEL = 1024u,  // SF 7-10: k_frames where k_wave would run
-                                   // (the matrix-core symbol tiles' tests,
+                                   // (the certificate tests on k_frames,
                                    // tests/test_gpu_certificate.py)
 };
 constexpr unsigned kTestFlags =

@@ -1,9 +1,9 @@
 // lphy_wave.h — fused single launch for SF 7-12 (N = 128 .. 4096): one
 // wavefront per unit of 64 x 64 complex values, i.e. one symbol at SF 12,
 // 2 / 4 / 8 / 16 / 32 symbols at SF 11 / 10 / 9 / 8 / 7 (SF 7-10: units
-// spanning frames, WSchedSpan), no workgroup barrier in the loop.  Included by lphy_kernels.h inside its anonymous
-// namespace, after k_frames (it reuses SymCtx, EstFold, the certificate and
-// the speculative normalisation of the SF <= 10 path).
+// spanning frames, WSchedSpan), no workgroup barrier in the loop.  It reuses
+// SymCtx, EstFold and the certificate (lphy_demod.h) and the speculative
+// normalisation of the SF <= 10 path (lphy_frames.h).
 //
 // The reference demodulates a frame in one pass at every SF
 // (/root/reference/src/phy/LoRaDemod.cpp:142-176, phy.cpp:204-238) with
@@ -52,6 +52,11 @@
 // 160 KiB of a CU at SF 12, one 256-thread workgroup per CU.  SF 12 with
 // the Hann window (round 6, modes 0 / 2): 3 waves (192 threads) x 32 KiB +
 // the down-chirp + the window's N floats, 144 KiB (wave_wpb).
+#pragma once
+#include "lphy_demod.h"
+#include "lphy_frames.h"
+
+namespace {
 
 // unroll of the LDS-DMA's run of shifted windows: 4 (the loop's counter,
 // compare and branch per 1 KiB piece were a third of a piece's ~8
@@ -1403,7 +1408,7 @@ struct WFrame {
 // waves per workgroup of k_wave<SF, MODE>: 4, but 3 at SF 12 with the
 // window (modes 0 / 2: the window's table does not fit beside four 32 KiB
 // buffers and the down-chirp; SF 12 mode 1 with the window stays on the
-// separate launches, wave_fit: its k_wave spilled 212 B per lane)
+// separate launches, lphy_route.h wave_kernel: its k_wave spilled 212 B per lane)
 template <int SF, int MODE>
 __host__ __device__ constexpr int wave_wpb() {
     return (SF == 12 && (MODE & kWinBit) != 0) ? 3 : WGeo<SF>::WPB;
@@ -2029,3 +2034,5 @@ __global__ __launch_bounds__(256, 1) void k_wave(FrameArgs P) {
     WPH(7);
     WPH_FLUSH(A)
 }
+
+}  // namespace

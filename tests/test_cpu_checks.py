@@ -4,7 +4,9 @@
   cover the fast path, the > 120 rad large-argument path, negatives,
   subnormals, infinities and NaN;
 * csrc/lphy_fft.h's index algebra (LDS address bijection, lane/element bit
-  split, every position touched once per pass) for SF 1-12."""
+  split, every position touched once per pass) for SF 1-12;
+* csrc/lphy_route.h (which kernels a demod call runs on) over the whole grid
+  of call shapes."""
 import subprocess
 from pathlib import Path
 
@@ -12,6 +14,7 @@ import pytest
 
 ROOT = Path(__file__).resolve().parents[1]
 CPP = ROOT / "tests" / "cpp"
+CSRC = ROOT / "lora-sdr-lightweight-standalone-library-clean_amd" / "csrc"
 
 
 @pytest.fixture(scope="module")
@@ -21,6 +24,8 @@ def bins(tmp_path_factory):
                     str(d / "libm_check"), str(CPP / "libm_exact_check.cpp")], check=True)
     subprocess.run(["/opt/rocm/bin/hipcc", "-std=c++17", "-O1", "-o", str(d / "fft_layout"),
                     str(CPP / "fft_layout_check.hip")], check=True)
+    subprocess.run(["g++", "-O2", "-std=c++17", "-I", str(CSRC), "-o", str(d / "route_check"),
+                    str(CPP / "route_check.cpp")], check=True)
     return d
 
 
@@ -65,6 +70,18 @@ def test_fft_layout_algebra(bins):
     r = subprocess.run([str(bins / "fft_layout")], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     assert r.stdout.count(": ok") == 12, r.stdout
+
+
+def test_route_grid(bins):
+    """lphy_route.h's route() over SF 1-12 x osr x mode x window x frame
+    lengths around a k_wave unit x batch sizes around the fused crossover x
+    the flags that steer it: equal to the decision as it stood when it was
+    spread over lphy_hip.hip and the launch templates (written out in
+    route_check.cpp), and every shape routed to k_frames / k_wave has an
+    instantiated kernel."""
+    r = subprocess.run([str(bins / "route_check")], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "mismatches=0" in r.stdout and "shapes=248832 " in r.stdout, r.stdout
 
 
 @pytest.mark.parametrize("what", ["logf", "log10"])

@@ -142,7 +142,7 @@ def test_frames_kernel_threshold_straddled(oracle, lphy, sf):
     _assert_straddle(rows, 64, thr)
     # The product library (lib/liblphy_hip.so) takes k_frames for frames
     # shorter than a wave unit (4096 / N symbols: k_wave's units span frames
-    # only from there, lphy_hip.hip wave_fit): the same sweep on such frames
+    # only from there, csrc/lphy_route.h): the same sweep on such frames
     # through the shipped code objects, no test flag.
     nsym = {7: 20, 8: 10}[sf]
     dp = lphy.Demodulator(sf)

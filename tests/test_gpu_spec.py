@@ -85,10 +85,12 @@ def test_speculative_normalisation(oracle, lphy, sf, nf, mode):
 def test_estimate_maxabs_in_symbol0(oracle, lphy, sf, how):
     """Frames whose max-abs lies in sync symbol 0, with symbol 1's own
     maximum smaller but still > 1: both estimate units must be scaled by the
-    frame's (symbol 0's) maximum, LoRaDemod.cpp:60-78.  Hann windows and
-    LPHY_F_EXACT_ROTATION route SF 9-10 modes 1/2 to k_frames, whose EB tiles
+    frame's (symbol 0's) maximum, LoRaDemod.cpp:60-78.  LPHY_F_EXACT_ROTATION
+    routes SF 9-10 modes 1/2 to k_frames (csrc/lphy_route.h), whose EB tiles
     fold the estimate symbols' max-abs only when both units share a tile
-    (SF <= 9); at SF 10 the two-symbol scan must supply it."""
+    (SF <= 9); at SF 10 the two-symbol scan must supply it.  With the Hann
+    window these frames run on the windowed k_wave, units spanning frames,
+    whose estimate unit holds both symbols of a frame."""
     N = 1 << sf
     rng = np.random.default_rng(1000 + sf)
     base = oracle.modulate(oracle.encode(bytes(range(12))), sf)

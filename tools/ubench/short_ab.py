@@ -1,6 +1,6 @@
 """A/B of one-SF library variants on the frames shorter than a wave unit
-(tools/shapes_perf.py's short16 / short8 rows), e.g. the f16 matrix-core
-symbol tiles of k_frames against -DLPHY_NO_MFMA.  Timing aid only.
+(tools/shapes_perf.py's short16 / short8 rows), which k_frames takes at
+SF 7-8 (csrc/lphy_route.h).  Timing aid only.
   python tools/ubench/short_ab.py <sf> <variant> ...   (GPU box; var_<variant>.so)"""
 import sys
 from pathlib import Path
