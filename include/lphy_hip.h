@@ -22,6 +22,8 @@
  *                          flag LPHY_F_DECODE adds, per frame:
  *                            lora_phy::decode / lora_decode src/phy/phy.cpp:245-261,
  *                            src/phy/LoRaDecoder.cpp:7-21
+ *   lphy_hip_demod_ragged  the same three modes for frames of different lengths
+ *                          in one call (lphy_ragged_desc, below)
  *   lphy_hip_decode_batch  lora_phy::decode / lora_decode on device symbols
  *   lphy_hip_estimate_batch lora_phy::estimate_offsets src/phy/phy.cpp:81-148
  *   lphy_hip_modulate_batch lora_phy::lora_modulate  src/phy/LoRaMod.cpp:8-43
@@ -157,6 +159,71 @@ int lphy_hip_demod_batch(lphy_hip_ctx* ctx, const float* d_iq, size_t frames,
                          size_t frame_samples, uint16_t* d_syms,
                          uint8_t* d_bytes, lphy_frame_meta* d_meta, int mode,
                          unsigned flags, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Ragged batches: frames of different lengths in one call.
+ *
+ * Frame f is described by record f of `frames + 1` descriptors; record
+ * [frames] holds the totals.  Frame f gets exactly what the uniform call
+ * (and the reference) returns for that frame alone on `samples` samples:
+ * its symbols at d_syms + sym_offset, its lphy_frame_meta at d_meta + f and,
+ * with LPHY_F_DECODE, its bytes at d_bytes + sym_offset/2.
+ *
+ * lphy_hip_ragged_layout fills the descriptors for frames packed back to
+ * back (outputs packed by lphy_hip_syms_per_frame, every sym_offset even).
+ * Callers may write their own, with gaps between frames in the IQ or in the
+ * outputs and frames in any address order, as long as
+ *   - no two frames overlap in the outputs (slots between them are left
+ *     untouched),
+ *   - unit_offset is the exclusive prefix sum of samples / N in record
+ *     order, starting at 0, with the total in record [frames], and
+ *   - sym_offset is even when LPHY_F_DECODE is set.
+ *
+ * Per-frame status: what the uniform call reports through its return value
+ * for a frame length becomes meta[f].status, and the frame writes nothing
+ * else: mode 0 with samples % N != 0 gives -EINVAL, mode 0 with fewer than
+ * two symbols -ERANGE, mode 2 with samples % N != 0 -EINVAL, and a frame of
+ * samples >= 2^31 -ERANGE.  -ERANGE under LPHY_F_NO_SCRATCH and -EINVAL for
+ * an odd decode count are reported as by lphy_hip_demod_batch.
+ *
+ * Scope: SF 7-12, osr 1, window none or Hann, modes 0-2, flags
+ * LPHY_F_DECODE and LPHY_F_NO_SCRATCH.  Anything else - the stage flags,
+ * LPHY_F_UNFUSED, the test build's flags, an osr > 1 context, SF < 7 -
+ * returns -ENOTSUP.  Limits (-ERANGE from lphy_hip_ragged_layout and the
+ * host form): any samples >= 2^31, or 2^32 or more whole symbols in the call.
+ * Launches: three symbol-parallel kernels (per-frame prologue, per-symbol
+ * rotate + FFT + argmax with the reference's per-sample rotation, per-frame
+ * finalisation); the call allocates nothing on the device.
+ * --------------------------------------------------------------------- */
+typedef struct lphy_ragged_desc {   /* 32 bytes; frames + 1 records */
+    uint64_t iq_offset;    /* first sample of frame f, in samples from d_iq   */
+    uint64_t samples;      /* the frame's sample_count (any value, 0 allowed) */
+    uint64_t sym_offset;   /* frame's first output symbol, from d_syms        */
+    uint64_t unit_offset;  /* exclusive prefix of whole symbols per frame     */
+} lphy_ragged_desc;        /* record [frames] holds the totals (samples = 0)  */
+
+/* Host-only, no device work.  From h_samples[frames] fills h_desc[frames+1].
+ * Returns 0, -EINVAL (null pointer, bad mode) or -ERANGE (the limits above). */
+int lphy_hip_ragged_layout(const lphy_hip_ctx* ctx, const uint64_t* h_samples,
+                           size_t frames, int mode, lphy_ragged_desc* h_desc);
+
+/* Demodulate `frames` frames described by d_desc (device memory, frames + 1
+ * records), asynchronously on `stream`.  d_bytes may be NULL unless
+ * LPHY_F_DECODE.  frames == 0 returns 0. */
+int lphy_hip_demod_ragged(lphy_hip_ctx* ctx, const float* d_iq,
+                          const lphy_ragged_desc* d_desc, size_t frames,
+                          uint16_t* d_syms, uint8_t* d_bytes,
+                          lphy_frame_meta* d_meta, int mode, unsigned flags,
+                          void* stream);
+
+/* The same on host buffers, through the context's stream and staging like
+ * lphy_hip_demod_host.  h_iq, h_syms and h_bytes span the descriptors' extent
+ * (the largest iq_offset + samples, and sym_offset plus the frame's symbols);
+ * output slots no frame owns keep the caller's values. */
+int lphy_hip_demod_ragged_host(lphy_hip_ctx* ctx, const float* h_iq,
+                               const lphy_ragged_desc* h_desc, size_t frames,
+                               uint16_t* h_syms, uint8_t* h_bytes,
+                               lphy_frame_meta* h_meta, int mode, unsigned flags);
 
 /* Hamming(8,4)sx decode + sx1272 CRC of device symbols: frame f holds
  * syms_per_frame symbols at d_syms + f*syms_per_frame and yields

@@ -59,6 +59,19 @@ struct FinalArgs {
     int set_sync;
 };
 
+// lphy_hip_demod_ragged (lphy_ragged.h): the call's tables, flags and output
+// bases in A; what DemodArgs holds once per call for frames of one length
+// (iq, syms, meta, frame_samples, total_syms, out_per_frame, est_units) the
+// ragged kernels fill per frame from its descriptor (frame_view).
+struct RaggedArgs {
+    DemodArgs A;
+    const lphy_ragged_desc* desc;  // A.frames + 1 records
+    uint8_t* bytes;                // LPHY_F_DECODE output base or nullptr
+    unsigned long long units_hint; // whole symbols of the call when the host knows them, else 0
+    int shift;                     // sf - 4 (sync word nibbles)
+    int decode;
+};
+
 // Per-SF launch entry points (one table per lphy_sf.hip instance)
 struct SfOps {
     int (*demod)(const DemodArgs&, hipStream_t, bool prologue, bool symbols, int per_cu);
@@ -68,6 +81,8 @@ struct SfOps {
     int (*estimate)(const DemodArgs&, hipStream_t);
     // debug build: read (and reset) this SF's failed index checks (else null)
     int (*violations)(unsigned long long* out, int reset);
+    // lphy_hip_demod_ragged: prologue, symbols and finalisation (SF 7-12)
+    int (*ragged)(const RaggedArgs&, hipStream_t);
 };
 extern const SfOps sf_ops_1, sf_ops_2, sf_ops_3, sf_ops_4, sf_ops_5, sf_ops_6,
     sf_ops_7, sf_ops_8, sf_ops_9, sf_ops_10, sf_ops_11, sf_ops_12;

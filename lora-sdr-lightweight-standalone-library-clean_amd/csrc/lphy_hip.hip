@@ -7,6 +7,7 @@
 #include "lphy_args.h"
 #include "lphy_final.h"
 #include "lphy_mod.h"
+#include "lphy_ragged_layout.h"
 #include "lphy_route.h"
 #include "lphy_testing.h"
 
@@ -512,6 +513,58 @@ int demod_batch_impl(lphy_hip_ctx* c, const float* d_iq, size_t frames, size_t f
 }
 }  // namespace
 
+// ---- ragged batches (lphy_ragged.h) ---------------------------------------
+int lphy_hip_ragged_layout(const lphy_hip_ctx* c, const uint64_t* h_samples, size_t frames, int mode,
+                           lphy_ragged_desc* h_desc) {
+    if (!c) return -EINVAL;
+    return ragged_layout((uint64_t)c->N * c->osr, h_samples, frames, mode, h_desc);
+}
+
+namespace {
+// units_hint: the call's whole symbols when the caller's table is on the host
+int demod_ragged_impl(lphy_hip_ctx* c, const float* d_iq, const lphy_ragged_desc* d_desc, size_t frames,
+                      uint16_t* d_syms, uint8_t* d_bytes, lphy_frame_meta* d_meta, int mode, unsigned flags,
+                      hipStream_t st, unsigned long long units_hint) {
+    if (!c || !d_iq || !d_desc || !d_meta || !d_syms) return -EINVAL;
+    if (mode < 0 || mode > 2) return -EINVAL;
+    if (flags & ~(unsigned)(LPHY_F_DECODE | LPHY_F_NO_SCRATCH)) return -ENOTSUP;
+    if (c->osr != 1 || c->sf < 7) return -ENOTSUP;
+    if ((flags & LPHY_F_DECODE) && !d_bytes) return -EINVAL;
+    if (frames == 0) return 0;
+    if (frames > 0x7fffffffULL) return -ERANGE;
+    const SfOps* ops = sf_ops(c->sf);
+    if (!ops || !ops->ragged) return -ENOTSUP;  // (an experiment build without this SF's object)
+    HIP_OK(hipSetDevice(c->device));
+    RaggedArgs R{};
+    DemodArgs& A = R.A;
+    A.iq = reinterpret_cast<const cf32*>(d_iq);
+    A.tw = c->d_tw;
+    A.down = c->d_down;
+    A.win = c->window == LPHY_WINDOW_HANN ? c->d_win : nullptr;
+    A.syms = d_syms;
+    A.meta = d_meta;
+    A.frames = frames;
+    A.osr = 1;
+    A.power_scale = c->power_scale;
+    A.mode = mode;
+    A.no_scratch = (flags & LPHY_F_NO_SCRATCH) ? 1 : 0;
+    A.exact_rotation = 1;
+    A.counters = c->d_counters;
+    R.desc = d_desc;
+    R.bytes = (flags & LPHY_F_DECODE) ? d_bytes : nullptr;
+    R.units_hint = units_hint;
+    R.shift = (int)c->sf - 4;
+    R.decode = (flags & LPHY_F_DECODE) ? 1 : 0;
+    return ops->ragged(R, st);
+}
+}  // namespace
+
+int lphy_hip_demod_ragged(lphy_hip_ctx* c, const float* d_iq, const lphy_ragged_desc* d_desc, size_t frames,
+                          uint16_t* d_syms, uint8_t* d_bytes, lphy_frame_meta* d_meta, int mode,
+                          unsigned flags, void* stream) {
+    return demod_ragged_impl(c, d_iq, d_desc, frames, d_syms, d_bytes, d_meta, mode, flags, (hipStream_t)stream, 0);
+}
+
 #ifdef LPHY_PROFILE_PHASES
 // experiments only: read and clear the kernels' per-phase clock sums (8)
 int lphy_hip_phase_cycles(lphy_hip_ctx* c, unsigned long long* out8) {
@@ -903,6 +956,54 @@ int lphy_hip_demod_host(lphy_hip_ctx* c, const float* h_iq, size_t frames,
     HIP_OK(hipMemcpyAsync(h_meta, d_meta, meta_n, hipMemcpyDeviceToHost, st));
     if (h_syms && per) HIP_OK(hipMemcpyAsync(h_syms, d_syms, syms_n, hipMemcpyDeviceToHost, st));
     if (h_bytes && decode && per / 2) HIP_OK(hipMemcpyAsync(h_bytes, d_bytes, bytes_n, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    return 0;
+}
+
+// The ragged call on host buffers: IQ, descriptors and the caller's output
+// slots in (slots no frame owns come back as they went), the three launches,
+// symbols / bytes / records out; the context's stream and staging.
+int lphy_hip_demod_ragged_host(lphy_hip_ctx* c, const float* h_iq, const lphy_ragged_desc* h_desc, size_t frames,
+                               uint16_t* h_syms, uint8_t* h_bytes, lphy_frame_meta* h_meta, int mode,
+                               unsigned flags) {
+    if (!c || !h_desc || !h_meta) return -EINVAL;
+    if (mode < 0 || mode > 2) return -EINVAL;
+    if (flags & ~(unsigned)(LPHY_F_DECODE | LPHY_F_NO_SCRATCH)) return -ENOTSUP;
+    if (c->osr != 1 || c->sf < 7) return -ENOTSUP;
+    const bool decode = (flags & LPHY_F_DECODE) != 0;
+    if (decode && !h_bytes) return -EINVAL;
+    if (frames == 0) return 0;
+    if (frames > 0x7fffffffULL) return -ERANGE;
+    uint64_t iq_samples = 0, out_syms = 0;
+    if (int rc = ragged_extent(c->N, h_desc, frames, mode, &iq_samples, &out_syms)) return rc;
+    if ((iq_samples && !h_iq) || (out_syms && !h_syms)) return -EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_OK(hipSetDevice(c->device));
+    const size_t iq_n = (size_t)iq_samples * sizeof(cf32), desc_n = (frames + 1) * sizeof(lphy_ragged_desc);
+    const size_t syms_n = (size_t)out_syms * sizeof(uint16_t), bytes_n = (size_t)(out_syms + 1) / 2;
+    const size_t meta_n = frames * sizeof(lphy_frame_meta);
+    const size_t o_desc = align_up(std::max<size_t>(1, iq_n)), o_syms = o_desc + align_up(desc_n);
+    const size_t o_bytes = o_syms + align_up(std::max<size_t>(1, syms_n));
+    const size_t o_meta = o_bytes + align_up(std::max<size_t>(1, bytes_n));
+    int rc = ensure_host_stage(c, o_meta + align_up(meta_n));
+    if (rc) return rc;
+    char* base = (char*)c->d_stage;
+    hipStream_t st = c->stream;
+    if (iq_n) HIP_OK(hipMemcpyAsync(base, h_iq, iq_n, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(base + o_desc, h_desc, desc_n, hipMemcpyHostToDevice, st));
+    if (syms_n) HIP_OK(hipMemcpyAsync(base + o_syms, h_syms, syms_n, hipMemcpyHostToDevice, st));
+    if (decode && bytes_n) HIP_OK(hipMemcpyAsync(base + o_bytes, h_bytes, bytes_n, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemsetAsync(base + o_meta, 0, meta_n, st));
+    rc = demod_ragged_impl(c, (const float*)base, (const lphy_ragged_desc*)(base + o_desc), frames,
+                           (uint16_t*)(base + o_syms), decode ? (uint8_t*)(base + o_bytes) : nullptr,
+                           (lphy_frame_meta*)(base + o_meta), mode, flags, st, h_desc[frames].unit_offset);
+    if (rc) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    HIP_OK(hipMemcpyAsync(h_meta, base + o_meta, meta_n, hipMemcpyDeviceToHost, st));
+    if (syms_n) HIP_OK(hipMemcpyAsync(h_syms, base + o_syms, syms_n, hipMemcpyDeviceToHost, st));
+    if (decode && bytes_n) HIP_OK(hipMemcpyAsync(h_bytes, base + o_bytes, bytes_n, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     return 0;
 }

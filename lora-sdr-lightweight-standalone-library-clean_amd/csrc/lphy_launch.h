@@ -10,6 +10,7 @@
 #include "lphy_demod.h"
 #include "lphy_frames.h"
 #include "lphy_post.h"
+#include "lphy_ragged.h"
 #include "lphy_route.h"
 #include "lphy_wave.h"
 
@@ -194,6 +195,36 @@ int launch_post_sf(int mode, const DemodArgs& A, const FinalArgs& F, bool fix, b
         HIP_OK(hipGetLastError());
         return 0;
     });
+}
+
+// lphy_hip_demod_ragged (lphy_ragged.h), SF 7-12: prologue, symbols,
+// finalisation.  The symbol kernel's persistent grid covers the call's whole
+// symbols when the host knows them (units_hint), else the device (the
+// workgroups past the last unit leave at once).
+template <int SF>
+int launch_ragged_sf(const RaggedArgs& R, hipStream_t st) {
+    if constexpr (SF < 7) {
+        (void)R; (void)st;
+        return -ENOTSUP;
+    } else {
+        using G = Geo<SF>;
+        constexpr int FPW = G::T >= 2 ? G::T / 2 : 1;
+        const unsigned long long frames = R.A.frames;
+        hipLaunchKernelGGL(k_rg_prologue<SF>, dim3((unsigned)((frames + FPW - 1) / FPW)), dim3(kTile), 0, st, R);
+        with_mode<true, false>(R.A.mode, R.A.win != nullptr, false, [&](auto m) {
+            constexpr int MODE = decltype(m)::value;
+            unsigned long long grid = (unsigned long long)resident_grid<&k_rg_demod<SF, MODE>>();
+            if (R.units_hint) {
+                const unsigned long long tiles = (R.units_hint + G::T - 1) / G::T;
+                if (grid > tiles) grid = tiles;
+            }
+            hipLaunchKernelGGL((k_rg_demod<SF, MODE>), dim3((unsigned)grid), dim3(kTile), 0, st, R);
+            return 0;
+        });
+        hipLaunchKernelGGL(k_rg_final<SF>, dim3((unsigned)((frames + kTile - 1) / kTile)), dim3(kTile), 0, st, R);
+        HIP_OK(hipGetLastError());
+        return 0;
+    }
 }
 
 template <int SF>

@@ -17,6 +17,7 @@ template int launch_frames_sf<LPHY_SF>(const DemodArgs&, hipStream_t);
 template int launch_wave_sf<LPHY_SF>(const DemodArgs&, hipStream_t);
 template int launch_post_sf<LPHY_SF>(int, const DemodArgs&, const FinalArgs&, bool, bool, hipStream_t);
 template int launch_estimate_sf<LPHY_SF>(const DemodArgs&, hipStream_t);
+template int launch_ragged_sf<LPHY_SF>(const RaggedArgs&, hipStream_t);
 }  // namespace
 
 #ifdef LPHY_DEBUG_BOUNDS
@@ -48,6 +49,7 @@ const SfOps LPHY_CAT(sf_ops_, LPHY_SF) = {
 #else
     nullptr,
 #endif
+    &launch_ragged_sf<LPHY_SF>,
 };
 }  // namespace lphy
 #endif

@@ -73,6 +73,11 @@ META_DTYPE = np.dtype([
 ])
 assert META_DTYPE.itemsize == 32
 
+# lphy_ragged_desc (include/lphy_hip.h): frames + 1 records per ragged call
+RAGGED_DESC_DTYPE = np.dtype([("iq_offset", "<u8"), ("samples", "<u8"), ("sym_offset", "<u8"),
+                              ("unit_offset", "<u8")])
+assert RAGGED_DESC_DTYPE.itemsize == 32
+
 _vp = C.c_void_p
 _sz = C.c_size_t
 
@@ -88,6 +93,7 @@ EXPORTS = (
     "lphy_hip_whiten_batch", "lphy_hip_hamming_batch", "lphy_hip_checksum_batch",
     "lphy_hip_lora_encode_batch", "lphy_hip_lorawan_mic_batch", "lphy_hip_lorawan_parse_batch",
     "lphy_hip_lorawan_mic_host",
+    "lphy_hip_ragged_layout", "lphy_hip_demod_ragged", "lphy_hip_demod_ragged_host",
 )
 
 WHITEN_SX1232, WHITEN_SX1272, WHITEN_SX1272_LFSR = 0, 1, 2
@@ -141,6 +147,9 @@ def load(path: Path | None = None) -> C.CDLL:
     L.lphy_hip_syms_per_frame.argtypes = [_vp, _sz, C.c_int]
     L.lphy_hip_syms_per_frame.restype = _sz
     L.lphy_hip_demod_batch.argtypes = [_vp, _vp, _sz, _sz, _vp, _vp, _vp, C.c_int, C.c_uint, _vp]
+    L.lphy_hip_ragged_layout.argtypes = [_vp, _vp, _sz, C.c_int, _vp]
+    L.lphy_hip_demod_ragged.argtypes = [_vp, _vp, _vp, _sz, _vp, _vp, _vp, C.c_int, C.c_uint, _vp]
+    L.lphy_hip_demod_ragged_host.argtypes = [_vp, _vp, _vp, _sz, _vp, _vp, _vp, C.c_int, C.c_uint]
     L.lphy_hip_decode_batch.argtypes = [_vp, _vp, _sz, _sz, _vp, _vp, _vp]
     L.lphy_hip_estimate_batch.argtypes = [_vp, _vp, _sz, _sz, _sz, _vp, _vp]
     L.lphy_hip_compensate.argtypes = [_vp, _vp, _sz, C.c_float, C.c_float, _vp]
@@ -252,6 +261,67 @@ class Demodulator:
         _chk(self.lib.lphy_hip_demod_batch(self.ctx, p_iq, frames, frame_samples,
                                            p_syms, p_pay, p_meta, mode, flags, stream),
              "lphy_hip_demod_batch")
+
+    # --- ragged batches: frames of different lengths in one call ---------
+    def ragged_layout(self, lengths, mode: int) -> np.ndarray:
+        """Descriptors (RAGGED_DESC_DTYPE, len(lengths) + 1 records) of frames
+        of `lengths` samples packed back to back; record [-1] holds the
+        totals (lphy_hip_ragged_layout)."""
+        n = np.ascontiguousarray(lengths, np.uint64).reshape(-1)
+        desc = np.zeros(n.size + 1, RAGGED_DESC_DTYPE)
+        _chk(self.lib.lphy_hip_ragged_layout(self.ctx, n.ctypes.data if n.size else None, n.size, mode,
+                                             desc.ctypes.data), "lphy_hip_ragged_layout")
+        return desc
+
+    def _ragged_extent(self, desc: np.ndarray, mode: int):
+        """(IQ samples, output symbols) the descriptors span."""
+        d = desc[:-1]
+        total = d["samples"] // np.uint64(self.N * self.osr)
+        per = np.where(total >= 2, total - np.minimum(total, 2), 0 if mode == MODE_DEMODULATE else total)
+        iq = int((d["iq_offset"] + d["samples"]).max()) if d.size else 0
+        out = int((d["sym_offset"] + per.astype(np.uint64)).max()) if d.size else 0
+        return iq, out
+
+    def demod_ragged(self, iq, desc, frames, syms, meta, mode, flags=0, payload=None, stream=None,
+                     iq_samples=None, out_syms=None):
+        """lphy_hip_demod_ragged on device tensors; `desc` is a device tensor
+        holding frames + 1 RAGGED_DESC_DTYPE records.  iq_samples / out_syms:
+        the extents the descriptors span (checked against the tensors)."""
+        dv = self.device
+        p_iq = _dev_buf(iq, "iq", dv, (iq_samples or 0) * 8, None)
+        p_desc = _dev_buf(desc, "desc", dv, (frames + 1) * 32, None)
+        p_syms = _dev_buf(syms, "syms", dv, (out_syms or 0) * 2, 2)
+        p_meta = _dev_buf(meta, "meta", dv, frames * 32, None)
+        p_pay = None
+        if flags & F_DECODE:
+            p_pay = _dev_buf(payload, "payload", dv, ((out_syms or 0) + 1) // 2, 1)
+        _chk(self.lib.lphy_hip_demod_ragged(self.ctx, p_iq, p_desc, frames, p_syms, p_pay, p_meta,
+                                            mode, flags, stream), "lphy_hip_demod_ragged")
+
+    def demod_ragged_host(self, iq_flat: np.ndarray, lengths_or_desc, mode: int, flags: int = 0,
+                          fill: int = 0):
+        """Demodulate frames of different lengths in one call.  `lengths_or_desc`
+        is a list of sample counts (frames packed back to back in `iq_flat`) or
+        a RAGGED_DESC_DTYPE array of frames + 1 records.  Returns (symbols,
+        bytes, meta, desc): flat arrays over the descriptors' extent, frame f's
+        symbols at desc["sym_offset"][f], its bytes at half of that.  Slots no
+        frame owns keep `fill` (symbols: fill, bytes: fill & 0xff)."""
+        a = np.asarray(lengths_or_desc)
+        desc = np.ascontiguousarray(a) if a.dtype == RAGGED_DESC_DTYPE else self.ragged_layout(a, mode)
+        frames = desc.size - 1
+        iq = np.ascontiguousarray(iq_flat, np.complex64).reshape(-1)
+        n_iq, n_out = self._ragged_extent(desc, mode)
+        if iq.size < n_iq:
+            raise ValueError(f"iq: {iq.size} samples, the descriptors span {n_iq}")
+        syms = np.full(max(n_out, 1), fill, np.uint16)
+        payload = np.full(max((n_out + 1) // 2, 1), fill & 0xFF, np.uint8)
+        meta = np.zeros(frames, META_DTYPE)
+        pad = np.zeros(1, np.complex64)
+        _chk(self.lib.lphy_hip_demod_ragged_host(self.ctx, (iq if iq.size else pad).ctypes.data,
+                                                 desc.ctypes.data, frames, syms.ctypes.data,
+                                                 payload.ctypes.data, meta.ctypes.data, mode, flags),
+             "lphy_hip_demod_ragged_host")
+        return syms, payload, meta, desc
 
     def modulate_batch(self, syms, frames, nsyms, iq, amplitude=1.0, sync=0x12, stream=None):
         dv = self.device
