@@ -13,7 +13,9 @@
  * Not carried over: the reference's internal FFT / detector classes
  * (kissfft.hh, LoRaDetector.hpp).  lora_demod_workspace keeps their storage
  * as opaque bytes (fft / detector are void*), so code that reaches into
- * those objects does not compile against this header.  The codec helpers
+ * those objects does not compile against this header.  The detector's
+ * outputs (peak bin, power, powerAvg, fIndex per window) come from the C
+ * ABI instead: lphy_hip_detect_batch in lphy_hip.h.  The codec helpers
  * (LoRaCodes.hpp) and the chirp generator (ChirpGenerator.hpp) are shipped
  * beside it.
  * Demodulation, offset estimation, compensation, decoding and modulation run

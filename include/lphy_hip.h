@@ -24,6 +24,8 @@
  *                            src/phy/LoRaDecoder.cpp:7-21
  *   lphy_hip_demod_ragged  the same three modes for frames of different lengths
  *                          in one call (lphy_ragged_desc, below)
+ *   lphy_hip_detect_batch  LoRaDetector<float>::detect include/lora_phy/LoRaDetector.hpp:39-74
+ *                          over a batch of windows (lphy_detect_rec, below)
  *   lphy_hip_decode_batch  lora_phy::decode / lora_decode on device symbols
  *   lphy_hip_estimate_batch lora_phy::estimate_offsets src/phy/phy.cpp:81-148
  *   lphy_hip_modulate_batch lora_phy::lora_modulate  src/phy/LoRaMod.cpp:8-43
@@ -224,6 +226,57 @@ int lphy_hip_demod_ragged_host(lphy_hip_ctx* ctx, const float* h_iq,
                                const lphy_ragged_desc* h_desc, size_t frames,
                                uint16_t* h_syms, uint8_t* h_bytes,
                                lphy_frame_meta* h_meta, int mode, unsigned flags);
+
+/* ------------------------------------------------------------------------
+ * The detector on a batch of windows: LoRaDetector<float>::detect
+ * (include/lora_phy/LoRaDetector.hpp:39-74), all four outputs per window.
+ *
+ * Window w feeds the detector N = 2^sf samples, x_i = iq[first + w*hop +
+ * i*step] for i = 0..N-1, prepared in this order:
+ *   1. with LPHY_DET_DECHIRP, times the context's down-chirp, x_i * down[i]
+ *      (the reference's complex product; the test-side dechirp of
+ *      tests/e2e_chain_test.cpp:80-93 on the window),
+ *   2. on a context created with LPHY_WINDOW_HANN, times win[i]
+ *      (LoRaDemod.cpp:96-97).
+ * No normalisation, no rotation.  hop < N makes the windows overlap (a
+ * sliding detector); step is the decimation: hop = 1, step = osr, windows =
+ * osr are the reference's osr phases of one symbol.  A frame's per-symbol SNR
+ * is power - power_avg with first = the frame's start, hop = N, step = 1.
+ *
+ * Every record holds what detect() returns for that input, bit for bit
+ * (where the reference gives a NaN, a NaN): an all-zero window gives index
+ * 0, power = power_avg = -inf, findex = 0; ties go to the lowest bin.
+ *
+ * Returns -EINVAL for a null ctx / iq / out, hop == 0, step == 0 or an
+ * unknown flag bit; -ENOTSUP for SF < 7; then 0 for windows == 0; -ERANGE
+ * for windows >= 2^32 or a last index first + (windows-1)*hop + (N-1)*step
+ * >= total_samples.  The device form is asynchronous on `stream`, allocates
+ * nothing and writes d_out[0 .. windows) only; the host form goes through the
+ * context's stream and staging like lphy_hip_demod_host.
+ *
+ * power_avg needs the reference's double-precision sum in bin order.  The
+ * kernel certifies its value from a parallel sum where it can and walks the
+ * bins in order where it cannot (a clean tone: total - maxValue cancels);
+ * lphy_hip_detect_serial_count reads (and with `reset` clears) the number of
+ * windows that took the walk on this context.  It synchronises the device.
+ * --------------------------------------------------------------------- */
+typedef struct lphy_detect_rec {   /* 16 bytes, one per window */
+    float    power;      /* detect()'s power                     */
+    float    power_avg;  /* detect()'s powerAvg                  */
+    float    findex;     /* detect()'s fIndex                    */
+    uint16_t index;      /* detect()'s return value (peak bin)   */
+    uint16_t reserved;   /* 0                                    */
+} lphy_detect_rec;
+
+enum lphy_detect_flags { LPHY_DET_DECHIRP = 1u };
+
+int lphy_hip_detect_batch(lphy_hip_ctx* ctx, const float* d_iq, size_t total_samples,
+                          size_t first, size_t hop, size_t step, size_t windows,
+                          lphy_detect_rec* d_out, unsigned flags, void* stream);
+int lphy_hip_detect_host(lphy_hip_ctx* ctx, const float* h_iq, size_t total_samples,
+                         size_t first, size_t hop, size_t step, size_t windows,
+                         lphy_detect_rec* h_out, unsigned flags);
+int lphy_hip_detect_serial_count(lphy_hip_ctx* ctx, unsigned long long* out, int reset);
 
 /* Hamming(8,4)sx decode + sx1272 CRC of device symbols: frame f holds
  * syms_per_frame symbols at d_syms + f*syms_per_frame and yields

@@ -72,6 +72,21 @@ struct RaggedArgs {
     int decode;
 };
 
+// lphy_hip_detect_batch (lphy_detect.h): window w feeds the detector the N
+// samples iq[first + w * hop + i * step]
+struct DetectArgs {
+    const cf32* iq;        // total_samples
+    const cf32* tw;        // N twiddles (KISS, forward)
+    const cf32* down;      // N down-chirp samples
+    const float* win;      // N window coefficients or nullptr
+    lphy_detect_rec* out;  // windows records
+    unsigned long long total_samples;
+    unsigned long long first, hop, step, windows;
+    int dechirp;           // LPHY_DET_DECHIRP
+    float power_scale;     // LoRaDetector.hpp:29
+    unsigned long long* counters;  // ctx counters (kCtrDetectSerial)
+};
+
 // Per-SF launch entry points (one table per lphy_sf.hip instance)
 struct SfOps {
     int (*demod)(const DemodArgs&, hipStream_t, bool prologue, bool symbols, int per_cu);
@@ -83,6 +98,8 @@ struct SfOps {
     int (*violations)(unsigned long long* out, int reset);
     // lphy_hip_demod_ragged: prologue, symbols and finalisation (SF 7-12)
     int (*ragged)(const RaggedArgs&, hipStream_t);
+    // lphy_hip_detect_batch: k_detect (SF 7-12)
+    int (*detect)(const DetectArgs&, hipStream_t);
 };
 extern const SfOps sf_ops_1, sf_ops_2, sf_ops_3, sf_ops_4, sf_ops_5, sf_ops_6,
     sf_ops_7, sf_ops_8, sf_ops_9, sf_ops_10, sf_ops_11, sf_ops_12;

@@ -565,6 +565,68 @@ int lphy_hip_demod_ragged(lphy_hip_ctx* c, const float* d_iq, const lphy_ragged_
     return demod_ragged_impl(c, d_iq, d_desc, frames, d_syms, d_bytes, d_meta, mode, flags, (hipStream_t)stream, 0);
 }
 
+// ---- the detector on a batch of windows (lphy_detect.h) --------------------
+namespace {
+// The argument checks of both forms, in the header's order; *last is the
+// largest sample index the call reads (windows > 0).  rc > 0: nothing to do.
+int detect_check(const lphy_hip_ctx* c, const void* iq, size_t total_samples, size_t first, size_t hop,
+                 size_t step, size_t windows, const void* out, unsigned flags, size_t* last) {
+    if (!c || !iq || !out || hop == 0 || step == 0) return -EINVAL;
+    if (flags & ~(unsigned)LPHY_DET_DECHIRP) return -EINVAL;
+    if (c->sf < 7) return -ENOTSUP;
+    if (windows == 0) return 1;
+    if ((unsigned long long)windows >= (1ull << 32)) return -ERANGE;
+    // first + (windows - 1) * hop + (N - 1) * step < total_samples, without overflow
+    if (total_samples == 0 || first > total_samples - 1) return -ERANGE;
+    size_t room = total_samples - 1 - first;
+    const size_t n1 = (size_t)c->N - 1;
+    if (step > room / n1) return -ERANGE;
+    room -= n1 * step;
+    if (windows > 1 && hop > room / (windows - 1)) return -ERANGE;
+    *last = first + (windows - 1) * hop + n1 * step;
+    return 0;
+}
+
+int detect_impl(lphy_hip_ctx* c, const float* d_iq, size_t total_samples, size_t first, size_t hop, size_t step,
+                size_t windows, lphy_detect_rec* d_out, unsigned flags, hipStream_t st) {
+    const SfOps* ops = sf_ops(c->sf);
+    if (!ops || !ops->detect) return -ENOTSUP;  // (an experiment build without this SF's object)
+    HIP_OK(hipSetDevice(c->device));
+    DetectArgs D{};
+    D.iq = reinterpret_cast<const cf32*>(d_iq);
+    D.tw = c->d_tw;
+    D.down = c->d_down;
+    D.win = c->window == LPHY_WINDOW_HANN ? c->d_win : nullptr;
+    D.out = d_out;
+    D.total_samples = total_samples;
+    D.first = first;
+    D.hop = hop;
+    D.step = step;
+    D.windows = windows;
+    D.dechirp = (flags & LPHY_DET_DECHIRP) ? 1 : 0;
+    D.power_scale = c->power_scale;
+    D.counters = c->d_counters;
+    return ops->detect(D, st);
+}
+}  // namespace
+
+int lphy_hip_detect_batch(lphy_hip_ctx* c, const float* d_iq, size_t total_samples, size_t first, size_t hop,
+                          size_t step, size_t windows, lphy_detect_rec* d_out, unsigned flags, void* stream) {
+    size_t last = 0;
+    if (int rc = detect_check(c, d_iq, total_samples, first, hop, step, windows, d_out, flags, &last))
+        return rc > 0 ? 0 : rc;
+    return detect_impl(c, d_iq, total_samples, first, hop, step, windows, d_out, flags, (hipStream_t)stream);
+}
+
+int lphy_hip_detect_serial_count(lphy_hip_ctx* c, unsigned long long* out, int reset) {
+    if (!c || !out) return -EINVAL;
+    HIP_OK(hipSetDevice(c->device));
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(out, c->d_counters + kCtrDetectSerial, sizeof(*out), hipMemcpyDeviceToHost));
+    if (reset) HIP_OK(hipMemset(c->d_counters + kCtrDetectSerial, 0, sizeof(*out)));
+    return 0;
+}
+
 #ifdef LPHY_PROFILE_PHASES
 // experiments only: read and clear the kernels' per-phase clock sums (8)
 int lphy_hip_phase_cycles(lphy_hip_ctx* c, unsigned long long* out8) {
@@ -1004,6 +1066,33 @@ int lphy_hip_demod_ragged_host(lphy_hip_ctx* c, const float* h_iq, const lphy_ra
     HIP_OK(hipMemcpyAsync(h_meta, base + o_meta, meta_n, hipMemcpyDeviceToHost, st));
     if (syms_n) HIP_OK(hipMemcpyAsync(h_syms, base + o_syms, syms_n, hipMemcpyDeviceToHost, st));
     if (decode && bytes_n) HIP_OK(hipMemcpyAsync(h_bytes, base + o_bytes, bytes_n, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    return 0;
+}
+
+// The detector on host buffers: the samples the windows span in (h_iq[first
+// .. last]), one launch, the records out; the context's stream and staging.
+int lphy_hip_detect_host(lphy_hip_ctx* c, const float* h_iq, size_t total_samples, size_t first, size_t hop,
+                         size_t step, size_t windows, lphy_detect_rec* h_out, unsigned flags) {
+    size_t last = 0;
+    if (int rc = detect_check(c, h_iq, total_samples, first, hop, step, windows, h_out, flags, &last))
+        return rc > 0 ? 0 : rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_OK(hipSetDevice(c->device));
+    const size_t span = last - first + 1;
+    const size_t iq_n = span * sizeof(cf32), out_n = windows * sizeof(lphy_detect_rec);
+    const size_t o_out = align_up(iq_n);
+    int rc = ensure_host_stage(c, o_out + align_up(out_n));
+    if (rc) return rc;
+    char* base = (char*)c->d_stage;
+    hipStream_t st = c->stream;
+    HIP_OK(hipMemcpyAsync(base, h_iq + 2 * first, iq_n, hipMemcpyHostToDevice, st));
+    rc = detect_impl(c, (const float*)base, span, 0, hop, step, windows, (lphy_detect_rec*)(base + o_out), flags, st);
+    if (rc) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    HIP_OK(hipMemcpyAsync(h_out, base + o_out, out_n, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     return 0;
 }

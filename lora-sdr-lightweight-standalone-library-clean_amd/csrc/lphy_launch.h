@@ -8,6 +8,7 @@
 #include <type_traits>
 
 #include "lphy_demod.h"
+#include "lphy_detect.h"
 #include "lphy_frames.h"
 #include "lphy_post.h"
 #include "lphy_ragged.h"
@@ -222,6 +223,34 @@ int launch_ragged_sf(const RaggedArgs& R, hipStream_t st) {
             return 0;
         });
         hipLaunchKernelGGL(k_rg_final<SF>, dim3((unsigned)((frames + kTile - 1) / kTile)), dim3(kTile), 0, st, R);
+        HIP_OK(hipGetLastError());
+        return 0;
+    }
+}
+
+// lphy_hip_detect_batch (lphy_detect.h), SF 7-12: one persistent launch over
+// tiles of Geo<SF>::T windows.
+template <int SF>
+int launch_detect_sf(const DetectArgs& D, hipStream_t st) {
+    if constexpr (SF < 7) {
+        (void)D; (void)st;
+        return -ENOTSUP;
+    } else {
+        auto go = [&](auto p) {
+            constexpr int PREP = decltype(p)::value;
+            constexpr int T = Geo<SF>::T;
+            unsigned long long grid = (unsigned long long)resident_grid<&k_detect<SF, PREP>>();
+            const unsigned long long tiles = (D.windows + T - 1) / T;
+            if (grid > tiles) grid = tiles;
+            hipLaunchKernelGGL((k_detect<SF, PREP>), dim3((unsigned)grid), dim3(kTile), 0, st, D);
+        };
+        const int prep = (D.dechirp ? kPrepDechirp : 0) | (D.win ? kPrepWindow : 0);
+        switch (prep) {
+            case 0: go(std::integral_constant<int, 0>{}); break;
+            case kPrepDechirp: go(std::integral_constant<int, kPrepDechirp>{}); break;
+            case kPrepWindow: go(std::integral_constant<int, kPrepWindow>{}); break;
+            default: go(std::integral_constant<int, kPrepDechirp | kPrepWindow>{}); break;
+        }
         HIP_OK(hipGetLastError());
         return 0;
     }

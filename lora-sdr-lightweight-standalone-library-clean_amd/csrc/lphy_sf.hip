@@ -18,6 +18,7 @@ template int launch_wave_sf<LPHY_SF>(const DemodArgs&, hipStream_t);
 template int launch_post_sf<LPHY_SF>(int, const DemodArgs&, const FinalArgs&, bool, bool, hipStream_t);
 template int launch_estimate_sf<LPHY_SF>(const DemodArgs&, hipStream_t);
 template int launch_ragged_sf<LPHY_SF>(const RaggedArgs&, hipStream_t);
+template int launch_detect_sf<LPHY_SF>(const DetectArgs&, hipStream_t);
 }  // namespace
 
 #ifdef LPHY_DEBUG_BOUNDS
@@ -50,6 +51,7 @@ const SfOps LPHY_CAT(sf_ops_, LPHY_SF) = {
     nullptr,
 #endif
     &launch_ragged_sf<LPHY_SF>,
+    &launch_detect_sf<LPHY_SF>,
 };
 }  // namespace lphy
 #endif

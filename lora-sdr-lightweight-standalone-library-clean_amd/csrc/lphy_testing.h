@@ -19,6 +19,7 @@
 constexpr int kCtrRecheck = 0;    // symbols re-run exactly (lphy_hip_recheck_count)
 constexpr int kCtrParseval = 1;   // test build: symbols the wave kernel certified by Parseval
 constexpr int kCtrModSerial = 2;  // frames k_mod_fast gave to its serial walk
+constexpr int kCtrDetectSerial = 3;  // windows k_detect summed in bin order (lphy_hip_detect_serial_count)
 constexpr int kCtrClocks = 8;     // timing builds only: 8 phase-clock sums (lphy_hip_phase_cycles)
 constexpr int kCounters = 16;
 

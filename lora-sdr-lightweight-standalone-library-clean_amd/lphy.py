@@ -78,6 +78,19 @@ RAGGED_DESC_DTYPE = np.dtype([("iq_offset", "<u8"), ("samples", "<u8"), ("sym_of
                               ("unit_offset", "<u8")])
 assert RAGGED_DESC_DTYPE.itemsize == 32
 
+
+# lphy_detect_rec (include/lphy_hip.h): one record per detector window
+class DetectRec(C.Structure):
+    _fields_ = [("power", C.c_float), ("power_avg", C.c_float), ("findex", C.c_float),
+                ("index", C.c_uint16), ("reserved", C.c_uint16)]
+
+
+assert C.sizeof(DetectRec) == 16
+DETECT_DTYPE = np.dtype([("power", "<f4"), ("power_avg", "<f4"), ("findex", "<f4"), ("index", "<u2"),
+                         ("reserved", "<u2")])
+assert DETECT_DTYPE.itemsize == 16
+DET_DECHIRP = 1  # lphy_hip_detect_*: the context's down-chirp on every window first
+
 _vp = C.c_void_p
 _sz = C.c_size_t
 
@@ -94,6 +107,7 @@ EXPORTS = (
     "lphy_hip_lora_encode_batch", "lphy_hip_lorawan_mic_batch", "lphy_hip_lorawan_parse_batch",
     "lphy_hip_lorawan_mic_host",
     "lphy_hip_ragged_layout", "lphy_hip_demod_ragged", "lphy_hip_demod_ragged_host",
+    "lphy_hip_detect_batch", "lphy_hip_detect_host", "lphy_hip_detect_serial_count",
 )
 
 WHITEN_SX1232, WHITEN_SX1272, WHITEN_SX1272_LFSR = 0, 1, 2
@@ -150,6 +164,9 @@ def load(path: Path | None = None) -> C.CDLL:
     L.lphy_hip_ragged_layout.argtypes = [_vp, _vp, _sz, C.c_int, _vp]
     L.lphy_hip_demod_ragged.argtypes = [_vp, _vp, _vp, _sz, _vp, _vp, _vp, C.c_int, C.c_uint, _vp]
     L.lphy_hip_demod_ragged_host.argtypes = [_vp, _vp, _vp, _sz, _vp, _vp, _vp, C.c_int, C.c_uint]
+    L.lphy_hip_detect_batch.argtypes = [_vp, _vp, _sz, _sz, _sz, _sz, _sz, _vp, C.c_uint, _vp]
+    L.lphy_hip_detect_host.argtypes = [_vp, _vp, _sz, _sz, _sz, _sz, _sz, _vp, C.c_uint]
+    L.lphy_hip_detect_serial_count.argtypes = [_vp, C.POINTER(C.c_ulonglong), C.c_int]
     L.lphy_hip_decode_batch.argtypes = [_vp, _vp, _sz, _sz, _vp, _vp, _vp]
     L.lphy_hip_estimate_batch.argtypes = [_vp, _vp, _sz, _sz, _sz, _vp, _vp]
     L.lphy_hip_compensate.argtypes = [_vp, _vp, _sz, C.c_float, C.c_float, _vp]
@@ -322,6 +339,35 @@ class Demodulator:
                                                  payload.ctypes.data, meta.ctypes.data, mode, flags),
              "lphy_hip_demod_ragged_host")
         return syms, payload, meta, desc
+
+    # --- the detector on a batch of windows (lphy_hip_detect_*) ----------
+    def detect_batch(self, iq, total_samples, first, hop, step, windows, out, flags=0, stream=None):
+        """LoRaDetector::detect on `windows` windows of device IQ: window w
+        reads iq[first + w*hop + i*step], i < N ([x down-chirp with
+        DET_DECHIRP] [x the context's Hann window]).  `out`: device tensor of
+        windows DETECT_DTYPE records (16 bytes each).  Asynchronous."""
+        dv = self.device
+        p_iq = _dev_buf(iq, "iq", dv, total_samples * 8, None)
+        p_out = _dev_buf(out, "out", dv, windows * 16, None)
+        _chk(self.lib.lphy_hip_detect_batch(self.ctx, p_iq, total_samples, first, hop, step, windows,
+                                            p_out, flags, stream), "lphy_hip_detect_batch")
+
+    def detect_host(self, iq: np.ndarray, first, hop, step, windows, flags=0) -> np.ndarray:
+        """The same on host samples; returns the DETECT_DTYPE record array."""
+        iq = np.ascontiguousarray(iq, np.complex64).reshape(-1)
+        out = np.zeros(windows, DETECT_DTYPE)
+        pad = np.zeros(1, DETECT_DTYPE)
+        _chk(self.lib.lphy_hip_detect_host(self.ctx, iq.ctypes.data, iq.size, first, hop, step, windows,
+                                           (out if windows else pad).ctypes.data, flags), "lphy_hip_detect_host")
+        return out
+
+    def detect_serial_count(self, reset: bool = True) -> int:
+        """Windows whose power_avg took the in-order walk of the bins because
+        the parallel sum could not certify it (device sync)."""
+        n = C.c_ulonglong(0)
+        _chk(self.lib.lphy_hip_detect_serial_count(self.ctx, C.byref(n), int(reset)),
+             "lphy_hip_detect_serial_count")
+        return int(n.value)
 
     def modulate_batch(self, syms, frames, nsyms, iq, amplitude=1.0, sync=0x12, stream=None):
         dv = self.device
