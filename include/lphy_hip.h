@@ -288,7 +288,16 @@ int lphy_hip_decode_batch(lphy_hip_ctx* ctx, const uint16_t* d_syms,
                           void* stream);
 
 /* estimate_offsets (phy.cpp:81-148) over the first `est_samples` samples of
- * each frame: writes meta[f].cfo / .time_offset / .t_off / .rate. */
+ * each frame (its est_samples / (N*osr) whole symbols; nothing after them is
+ * read): writes meta[f].cfo / .time_offset / .t_off / .rate, with
+ * t_off = (int)round(time_offset) and rate = -2*pi*cfo / N.  The call
+ * rewrites the whole record, not only those four fields: status = 0,
+ * scale = 1, have_sync = (frame_samples / (N*osr) >= 2), and sw0, sw1,
+ * sync_word, crc_ok and normalised = 0, whatever the record held before.
+ * With frames == 0, or est_samples shorter than one symbol, it returns 0 and
+ * writes nothing (phy.cpp:87,91).  est_samples > frame_samples (frames >= 1)
+ * gives -EINVAL and launches nothing: the estimate would read the next
+ * frame, and the last frame's past the end of d_iq. */
 int lphy_hip_estimate_batch(lphy_hip_ctx* ctx, const float* d_iq,
                             size_t frames, size_t frame_samples,
                             size_t est_samples, lphy_frame_meta* d_meta,

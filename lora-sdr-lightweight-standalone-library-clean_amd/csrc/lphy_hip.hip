@@ -668,7 +668,10 @@ int lphy_hip_estimate_batch(lphy_hip_ctx* c, const float* d_iq, size_t frames,
     if (!c || !d_iq || !d_meta) return -EINVAL;
     const size_t step = (size_t)c->N * c->osr;
     const size_t syms = est_samples / step;
-    if (syms == 0 || frames == 0) return 0;  // phy.cpp:87,91: nothing written
+    if (frames == 0) return 0;
+    // the estimate may not leave its frame (the last frame's would leave the buffer)
+    if (est_samples > frame_samples) return -EINVAL;
+    if (syms == 0) return 0;  // phy.cpp:87,91: nothing written
     if (syms * c->osr > 0x7fffffffULL) return -ERANGE;
     HIP_OK(hipSetDevice(c->device));
     DemodArgs A{};

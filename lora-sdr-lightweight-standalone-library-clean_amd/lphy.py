@@ -386,6 +386,17 @@ class Demodulator:
                                             p_pay, p_meta, stream),
              "lphy_hip_decode_batch")
 
+    def estimate_batch(self, iq, frames, frame_samples, est_samples, meta, stream=None):
+        """estimate_offsets over the first `est_samples` samples of each of
+        `frames` device frames; rewrites the frames' 32-byte `meta` records
+        (lphy_hip_estimate_batch).  Asynchronous."""
+        dv = self.device
+        p_iq = _dev_buf(iq, "iq", dv, frames * frame_samples * 8, None)
+        p_meta = _dev_buf(meta, "meta", dv, frames * 32, None)
+        _chk(self.lib.lphy_hip_estimate_batch(self.ctx, p_iq, frames, frame_samples, est_samples,
+                                              p_meta, stream),
+             "lphy_hip_estimate_batch")
+
     # --- streaming ingestion (lphy_hip_demod_stream) --------------------
     def demod_stream(self, fd: int, frame_samples: int, mode: int, flags: int = 0,
                      chunk_frames: int = 0, max_frames: int = 0, capacity: int = 0):

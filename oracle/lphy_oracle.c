@@ -352,8 +352,10 @@ size_t orc_lora_modulate(const uint16_t* syms, size_t n, float* out,
     const size_t step = N * osr;
     const float bws = (float)bw_hz / 125000.0f;
     float phase = 0.0f;
-    if (ampl > 1.0f) ampl = 1.0f;
-    if (ampl < -1.0f) ampl = -1.0f;
+    /* LoRaMod.cpp:18, std::max(-1.0f, std::min(1.0f, a)): std::min(1, a) is
+     * (a < 1) ? a : 1, so a NaN amplitude becomes 1 */
+    ampl = ampl < 1.0f ? ampl : 1.0f;
+    ampl = -1.0f < ampl ? ampl : -1.0f;
     unsigned shift = sf > 4 ? sf - 4 : 0;
     const uint16_t sw[2] = {(uint16_t)((sync >> 4) << shift),
                             (uint16_t)((sync & 0x0f) << shift)};

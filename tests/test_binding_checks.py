@@ -50,3 +50,7 @@ def test_demod_batch_argument_checks(lphy):
         d.decode_batch(syms, frames, per, pay[:-1], meta, stream=st)
     with pytest.raises(ValueError):
         d.modulate_batch(syms, frames, per, iq[:-2], stream=st)
+    with pytest.raises(ValueError):
+        d.estimate_batch(iq[:-2], frames, fs, 2 * 128, meta, stream=st)  # IQ short by one sample
+    with pytest.raises(ValueError):
+        d.estimate_batch(iq, frames, fs, 2 * 128, meta[:-1], stream=st)  # one meta byte short

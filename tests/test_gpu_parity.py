@@ -110,17 +110,24 @@ def test_modulate_bit_exact(oracle, lphy):
         np.testing.assert_array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
-@pytest.mark.parametrize("sf,osr,nf,nsyms", [(7, 1, 1, 64), (7, 1, 5, 64), (8, 1, 3, 64), (9, 1, 2, 64),
-                                              (5, 3, 4, 21), (7, 2, 2, 30), (3, 3, 3, 7), (2, 1, 2, 5),
-                                              (10, 1, 2, 64), (7, 1, 70, 64), (11, 2, 2, 30), (12, 1, 3, 20)])
-def test_modulate_batch_frames(oracle, lphy, sf, osr, nf, nsyms):
+# (the 125 kHz rows keep the ids they had before the bandwidth column)
+MOD_BATCH = [pytest.param(*c, 125000, id="-".join(map(str, c)))
+             for c in [(7, 1, 1, 64), (7, 1, 5, 64), (8, 1, 3, 64), (9, 1, 2, 64),
+                       (5, 3, 4, 21), (7, 2, 2, 30), (3, 3, 3, 7), (2, 1, 2, 5),
+                       (10, 1, 2, 64), (7, 1, 70, 64), (11, 2, 2, 30), (12, 1, 3, 20)]]
+MOD_BATCH += [(10, 1, 2, 64, 250000), (7, 1, 70, 64, 500000)]
+
+
+@pytest.mark.parametrize("sf,osr,nf,nsyms,bw", MOD_BATCH)
+def test_modulate_batch_frames(oracle, lphy, sf, osr, nf, nsyms, bw):
     """lphy_hip_modulate_batch, frame by frame == the oracle: k_mod_fast (f
     rows in LDS: up to SF 9 at 66 symbols, few frames, osr 2-3 too), its
     split form with the rows interleaved in the phase buffer (SF 10-12,
-    several frames, osr 2 at SF 11) and the batch form (70 frames)."""
+    several frames, osr 2 at SF 11) and the batch form (70 frames); the split
+    and batch forms at 250 and 500 kHz too (bw_scale 2 and 4)."""
     rng = np.random.default_rng(sf * 100 + nf)
     syms = rng.integers(0, 1 << min(sf, 8), (nf, nsyms), dtype=np.uint16)
-    d = lphy.Demodulator(sf, 125000, osr)
+    d = lphy.Demodulator(sf, bw, osr)
     dev = torch.device("cuda", 0)
     step = (1 << sf) * osr
     iq = torch.zeros(nf * (nsyms + 2) * step * 2, dtype=torch.float32, device=dev)
@@ -129,8 +136,45 @@ def test_modulate_batch_frames(oracle, lphy, sf, osr, nf, nsyms):
     torch.cuda.synchronize()
     got = iq.cpu().numpy().view(np.complex64).reshape(nf, -1)
     for f in range(nf):
-        b = oracle.modulate(syms[f], sf, osr=osr, sync=0x34)
+        b = oracle.modulate(syms[f], sf, osr=osr, bw_hz=bw, sync=0x34)
         np.testing.assert_array_equal(got[f].view(np.uint32), b.view(np.uint32), err_msg=f"frame {f}")
+
+
+@pytest.mark.parametrize("sf,osr,nf,nsyms,host", [
+    (7, 1, 1, 10, True),     # k_mod_fast, rows in LDS (and lphy_hip_modulate_host)
+    (10, 1, 2, 20, False),   # SF 10: 22 rows of 1028 floats + windows = 92 KB, in LDS where it allows that
+    (10, 1, 2, 64, False),   # split form: 66 such rows (276 KB) exceed any LDS, so they go to the phase buffer
+    (7, 1, 70, 64, False),   # batch form (k_mod_walk / k_mod_samples): 70 * 66 >= 4096 symbols
+    (5, 1, 1, 300, False),   # three-kernel form: 302 symbols > 256
+    (7, 2, 2, 30, False),    # osr > 1
+])
+def test_modulate_amplitude(oracle, lphy, sf, osr, nf, nsyms, host):
+    """The amplitude of lora_modulate (LoRaMod.cpp:18: clamped to [-1, 1], a
+    NaN amplitude becomes 1) times cos / sin in k_mod_sincos and
+    k_mod_samples == the oracle, every float bit, through each modulator
+    form.  test_oracle_vs_reference.py pins the oracle's amplitudes
+    (test_modulate_amplitude_bit_exact)."""
+    from test_oracle_vs_reference import AMPLITUDES, _nan_bits_equal
+    rng = np.random.default_rng(sf * 50 + nsyms)
+    syms = rng.integers(0, 1 << min(sf, 8), (nf, nsyms), dtype=np.uint16)
+    d = lphy.Demodulator(sf, 125000, osr)
+    dev = torch.device("cuda", 0)
+    step = (1 << sf) * osr
+    s_t = torch.from_numpy(syms.reshape(-1).astype(np.int16)).to(dev)
+    for a in AMPLITUDES:
+        want = np.stack([oracle.modulate(syms[f], sf, osr=osr, ampl=a, sync=0x34) for f in range(nf)])
+        iq = torch.full((nf * (nsyms + 2) * step * 2,), 7.0, dtype=torch.float32, device=dev)
+        d.modulate_batch(s_t, nf, nsyms, iq, a, 0x34, torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        got = [iq.cpu().numpy().reshape(nf, -1)]
+        if host:
+            got.append(d.modulate_host(syms[0], a, 0x34).view(np.float32).reshape(1, -1))
+        for g in got:
+            if a != a:
+                _nan_bits_equal(g, want.view(np.float32)[: g.shape[0]])
+            else:
+                np.testing.assert_array_equal(g.view(np.uint32), want.view(np.uint32)[: g.shape[0]],
+                                              err_msg=f"amplitude {a}")
 
 
 @pytest.mark.parametrize("sf", [5, 6, 7, 8, 9, 10, 11, 12])

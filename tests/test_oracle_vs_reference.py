@@ -230,6 +230,95 @@ def test_nonfinite_samples_bit_exact(oracle, reference, sf):
         _nan_bits_equal(fa.view(np.float32), fb.view(np.float32))
 
 
+# ---- estimate_offsets over many symbols (phy.cpp:81-148) ------------------
+# Input kinds of the estimate tests, here and in tests/test_gpu_estimate.py:
+# a noisy packet, noise (random peak phases: both unwrap loops of
+# phy.cpp:129-130 run), a packet with all-zero symbols (no bin beats
+# best_p = -1e30, so the symbol adds index 0, phase 0) and small noise.
+EST_KINDS = ("packet", "noise", "packet_gap", "packet_gap0", "noise_small")
+
+
+def _estimate_head(oracle, rng, kind, sf, osr, n):
+    """n whole symbols of estimate input of one kind.  packet: random symbols
+    with a carrier offset of 0.1-0.45 bin, a delay of 1-5 samples and noise at
+    0 dB; packet_gap: the same with symbol n // 2 zeroed, packet_gap0 with
+    symbol 0 zeroed too; noise: complex Gaussian, noise_small: scaled by 1e-3."""
+    step = (1 << sf) * osr
+    count = n * step
+    if kind in ("noise", "noise_small"):
+        return _iq(rng, count, 1e-3 if kind == "noise_small" else 1.0)
+    syms = rng.integers(0, 1 << min(sf, 8), n, dtype=np.uint16)
+    x = oracle.modulate(syms, sf, osr=osr).astype(np.complex128)
+    cfo = rng.uniform(0.1, 0.45) * rng.choice((-1.0, 1.0))
+    x = x * np.exp(2j * np.pi * cfo / step * np.arange(x.size))
+    x = np.concatenate([np.zeros(int(rng.integers(1, 6))), x])[:count]
+    x = (x + np.sqrt(0.5) * (rng.standard_normal(count) + 1j * rng.standard_normal(count))).astype(np.complex64)
+    if kind in ("packet_gap", "packet_gap0"):
+        x[(n // 2) * step:(n // 2 + 1) * step] = 0
+        if kind == "packet_gap0":
+            x[:step] = 0
+    else:
+        assert kind == "packet"
+    return x
+
+
+def _estimate_nonfinite(oracle, rng, sf, osr, n):
+    """Packets with a NaN sample in one symbol, an Inf sample in another
+    (the last), and both.  The NaN symbol's bins are all NaN: no valid peak."""
+    step = (1 << sf) * osr
+    base = _estimate_head(oracle, rng, "packet", sf, osr, n)
+    p_nan = (1 if n >= 3 else 0) * step + 5
+    p_inf = (n - 1) * step + 11
+    out = []
+    for nan, inf in ((True, False), (False, True), (True, True)):
+        x = base.copy()
+        if nan:
+            x[p_nan] = complex(np.nan, 3.0)
+        if inf:
+            x[p_inf] = complex(np.inf, 0.25)
+        out.append(x)
+    return out
+
+
+@pytest.mark.parametrize("sf,hann,ns", [(5, False, (1, 2, 9, 33)), (7, False, (1, 2, 9, 33)),
+                                        (7, True, (1, 2, 9, 33)), (9, True, (1, 2, 9, 33)),
+                                        (12, False, (1, 2, 5))],
+                         ids=["sf5", "sf7", "sf7-hann", "sf9-hann", "sf12"])
+def test_estimate_offsets_many_symbols_bit_exact(oracle, reference, sf, hann, ns):
+    """osr 1 over up to 33 symbols: the float sum of unwrapped phase
+    differences in symbol order, symbols without a valid peak, non-finite
+    samples.  tests/test_gpu_estimate.py holds the GPU to the oracle here."""
+    rng = np.random.default_rng(4100 + sf * 2 + hann)
+    for n in ns:
+        for kind in EST_KINDS:
+            if kind == "packet_gap0" and n < 2:
+                continue
+            x = _estimate_head(oracle, rng, kind, sf, 1, n)
+            a, b = oracle.estimate_offsets(x, sf, 1, hann), reference.estimate_offsets(x, sf, 1, hann)
+            np.testing.assert_array_equal(_bits(a), _bits(b), err_msg=f"n {n} {kind}")
+        for x in _estimate_nonfinite(oracle, rng, sf, 1, n):
+            _nan_bits_equal(oracle.estimate_offsets(x, sf, 1, hann), reference.estimate_offsets(x, sf, 1, hann))
+
+
+# ---- lora_modulate's amplitude (LoRaMod.cpp:18 clamp, std::polar) ----------
+AMPLITUDES = [0.5, -0.75, 0.0, 1.0, 1.5, -3.0, float("nan")]
+
+
+@pytest.mark.parametrize("sf", [7, 10])
+def test_modulate_amplitude_bit_exact(oracle, reference, sf):
+    """std::max(-1.0f, std::min(1.0f, a)): out-of-range amplitudes clamp, a
+    NaN amplitude becomes 1 (std::min keeps its first argument), negative
+    ones and 0 keep std::polar's signs (-0.0 included)."""
+    rng = np.random.default_rng(70 + sf)
+    syms = rng.integers(0, 1 << min(sf, 8), 6, dtype=np.uint16)
+    for a in AMPLITUDES:
+        _nan_bits_equal(oracle.modulate(syms, sf, ampl=a, sync=0x34).view(np.float32),
+                        reference.modulate(syms, sf, ampl=a, sync=0x34).view(np.float32))
+    one = reference.modulate(syms, sf, ampl=1.0, sync=0x34)
+    np.testing.assert_array_equal(reference.modulate(syms, sf, ampl=float("nan"), sync=0x34).view(np.uint32),
+                                  one.view(np.uint32))
+
+
 COMP_CASES = [  # sf, osr, cfo, time_offset
     (7, 1, 0.37, 95.54), (7, 1, -0.21, -12.4), (8, 1, 0.0, 0.0), (9, 2, 0.45, 300.2),
     (12, 1, -0.5, 1e9), (7, 1, 3.0, -2.6e9), (5, 4, 0.1, float("nan")), (10, 1, 1e-4, 0.49)]
