@@ -31,6 +31,10 @@
  *   lphy_hip_modulate_batch lora_phy::lora_modulate  src/phy/LoRaMod.cpp:8-43
  *                            (producer; bit-exact, used for synthetic IQ)
  *   lphy_hip_compensate    lora_phy::compensate_offsets src/phy/phy.cpp:150-180
+ *   lphy_hip_compensate_batch  the same for every frame of a batch, each with its
+ *   lphy_hip_compensate_ragged own offsets read on the device from its
+ *                          lphy_frame_meta (frames of one length / of different
+ *                          lengths, lphy_ragged_desc)
  *
  * Batch layout in HBM:
  *   IQ      interleaved float32 (I,Q) = std::complex<float>, frame f at
@@ -307,6 +311,60 @@ int lphy_hip_estimate_batch(lphy_hip_ctx* ctx, const float* d_iq,
 int lphy_hip_compensate(lphy_hip_ctx* ctx, float* d_iq, size_t count,
                         float cfo, float time_offset, void* stream);
 
+/* ------------------------------------------------------------------------
+ * compensate_offsets (phy.cpp:150-180) for every frame of a batch, each with
+ * its own offsets read on the device from d_meta[f].cfo / .time_offset: what
+ * lphy_hip_estimate_batch left there feeds it on the same stream, with no
+ * host copy between the two calls.  Only those two fields are read (not
+ * .rate, which is -2*pi*cfo/N without osr, nor .t_off: a caller may have
+ * filled cfo and time_offset alone); d_meta is not written.
+ *
+ * Frame f of `count` samples gets, bit for bit, what the reference gives for
+ * that frame alone, n = 0..count-1 within the frame:
+ *   rate = -2.0f * PI * cfo / ((float)N * (float)osr), in float, on the device;
+ *   off  = (int)std::round(time_offset) as x86-64 evaluates it (INT_MIN for a
+ *          NaN or a value out of int's range);
+ *   a shift applies iff off != INT_MIN and 0 < |off| < count; then, with
+ *   src = n - off, out[n] = (0 <= src < count) ? in[src] * cis(rate * (float)src) : 0;
+ *   without a shift out[n] = in[n] * cis(rate * (float)n).
+ * cis is the reference's sincosf pair and the product its std::complex
+ * product (with the Annex G recovery).  Frame indices are 64-bit.  Nothing
+ * outside a frame's own samples is read or written.
+ *
+ * Aliasing: d_out == d_in is in place, disjoint buffers are out of place;
+ * the uniform form returns -EINVAL for any other overlap of the two extents
+ * (frames * frame_samples samples each).  The ragged form cannot know its
+ * extent on the host: a partial overlap there is the caller's error, and
+ * ragged frames must not overlap each other.
+ *
+ * One fused rotate-and-shift launch, asynchronous on `stream`: 16 bytes of
+ * traffic per sample, no device allocation, no host read of d_meta.  Out of
+ * place every 1024-sample tile of every frame is a workgroup of its own (the
+ * ragged form: eight workgroups per frame).  In place a frame's tiles depend
+ * on each other when off != 0, so one workgroup owns the frame and walks its
+ * tiles in memmove order: in-place parallelism is per frame.  A batch of many
+ * frames fills the GPU either way; a single very long buffer is what
+ * lphy_hip_compensate is for.
+ *
+ * Returns -EINVAL for a null ctx, then 0 for frames == 0; -EINVAL for a null
+ * d_in, d_out, d_meta or d_desc; -ERANGE for frames >= 2^31 (uniform form:
+ * also when frames * frame_samples * 8 bytes overflows size_t); 0 for
+ * frame_samples == 0; -EINVAL for the partial overlap above.  All of it
+ * before any device call.
+ * --------------------------------------------------------------------- */
+int lphy_hip_compensate_batch(lphy_hip_ctx* ctx, const float* d_in, float* d_out,
+                              size_t frames, size_t frame_samples,
+                              const lphy_frame_meta* d_meta, void* stream);
+
+/* The same for frames of different lengths: frame f is d_desc[f].samples
+ * samples at d_desc[f].iq_offset (in samples), in d_in and in d_out alike.
+ * sym_offset and unit_offset are not read, nor is record [frames].  Gaps
+ * between frames in d_out keep their contents; a frame of 0 samples writes
+ * nothing. */
+int lphy_hip_compensate_ragged(lphy_hip_ctx* ctx, const float* d_in, float* d_out,
+                               const lphy_ragged_desc* d_desc, size_t frames,
+                               const lphy_frame_meta* d_meta, void* stream);
+
 /* lora_modulate (LoRaMod.cpp:8-43) for `frames` frames of `nsyms` symbols
  * each (d_syms + f*nsyms) into d_iq + 2*f*(nsyms+2)*N*osr floats; bit-exact
  * with the reference.  Producer for synthetic input, not on the timed path. */
@@ -329,6 +387,10 @@ int lphy_hip_estimate_host(lphy_hip_ctx* ctx, const float* h_iq,
                            size_t count, lphy_frame_meta* h_meta);
 int lphy_hip_compensate_host(lphy_hip_ctx* ctx, float* h_iq, size_t count,
                              float cfo, float time_offset);
+/* lphy_hip_compensate_batch on host buffers, in place (h_iq: frames *
+ * frame_samples samples, h_meta: frames records, read only). */
+int lphy_hip_compensate_batch_host(lphy_hip_ctx* ctx, float* h_iq, size_t frames,
+                                   size_t frame_samples, const lphy_frame_meta* h_meta);
 int lphy_hip_modulate_host(lphy_hip_ctx* ctx, const uint16_t* h_syms,
                            size_t nsyms, float* h_iq, float amplitude,
                            uint8_t sync);

@@ -720,6 +720,59 @@ int compensate_impl(lphy_hip_ctx* c, float* d_iq, size_t count, float cfo, float
     return 0;
 }
 
+// compensate_offsets for every frame of a batch, offsets read on the device
+// (k_comp_batch, lphy_mod.h): one launch, no scratch.  `slots` workgroups
+// share a frame out of place; in place (d_out == d_in) one owns it and walks
+// its tiles in memmove order.
+constexpr unsigned long long kCompMaxGrid = 1ull << 22;  // (x 256 threads stays below 2^32)
+
+extern "C++" {
+template <class GEO>
+int compensate_batch_launch(const lphy_hip_ctx* c, const float* d_in, float* d_out, GEO geo, size_t frames,
+                            unsigned slots, const lphy_frame_meta* d_meta, hipStream_t st) {
+    const cf32* in = reinterpret_cast<const cf32*>(d_in);
+    cf32* out = reinterpret_cast<cf32*>(d_out);
+    const bool in_place = d_in == d_out;
+    if (in_place) slots = 1;
+    const unsigned grid = (unsigned)std::min<unsigned long long>((unsigned long long)frames * slots, kCompMaxGrid);
+    if (in_place)
+        hipLaunchKernelGGL((k_comp_batch<GEO, true>), dim3(grid), dim3(kTile), 0, st, in, out, geo, d_meta,
+                           (unsigned long long)frames, slots, (int)c->N, (int)c->osr);
+    else
+        hipLaunchKernelGGL((k_comp_batch<GEO, false>), dim3(grid), dim3(kTile), 0, st, in, out, geo, d_meta,
+                           (unsigned long long)frames, slots, (int)c->N, (int)c->osr);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+}  // extern "C++"
+
+// The uniform form's argument checks (before any device call): 0 to go on,
+// 1 when there is nothing to do, or the error.
+int compensate_batch_check(const lphy_hip_ctx* c, const float* in, const float* out, size_t frames,
+                           size_t frame_samples, const lphy_frame_meta* meta) {
+    if (!c) return -EINVAL;
+    if (frames == 0) return 1;
+    if (!in || !out || !meta) return -EINVAL;
+    if (frames > 0x7fffffffULL) return -ERANGE;
+    if (frame_samples == 0) return 1;
+    size_t bytes = 0;
+    if (__builtin_mul_overflow(frames, frame_samples, &bytes) || __builtin_mul_overflow(bytes, sizeof(cf32), &bytes))
+        return -ERANGE;
+    // in place or disjoint; a partial overlap has no order that is right for every frame
+    const uintptr_t a = (uintptr_t)in, b = (uintptr_t)out;
+    if (a != b && a < b + bytes && b < a + bytes) return -EINVAL;
+    return 0;
+}
+
+int compensate_batch_impl(const lphy_hip_ctx* c, const float* d_in, float* d_out, size_t frames,
+                          size_t frame_samples, const lphy_frame_meta* d_meta, hipStream_t st) {
+    // one workgroup per tile (a frame's first output sample may sit half a 16-byte pair in)
+    const size_t tiles = (frame_samples + 1 + kCompTile - 1) / kCompTile;
+    const unsigned slots = (unsigned)std::min<size_t>(tiles, size_t(1) << 20);
+    return compensate_batch_launch(c, d_in, d_out, CompUniform{(unsigned long long)frame_samples}, frames, slots,
+                                   d_meta, st);
+}
+
 // lora_modulate (LoRaMod.cpp:8-43) for `frames` frames; `lent` (optional)
 // holds mod_scratch_bytes(): the per-symbol start phases, and below
 // mod_walk_all_below symbols every sample's phase too.
@@ -854,6 +907,24 @@ int lphy_hip_compensate(lphy_hip_ctx* c, float* d_iq, size_t count, float cfo,
     if (count == 0) return 0;
     HIP_OK(hipSetDevice(c->device));
     return compensate_impl(c, d_iq, count, cfo, time_offset, (hipStream_t)stream, nullptr);
+}
+
+int lphy_hip_compensate_batch(lphy_hip_ctx* c, const float* d_in, float* d_out, size_t frames,
+                              size_t frame_samples, const lphy_frame_meta* d_meta, void* stream) {
+    if (int rc = compensate_batch_check(c, d_in, d_out, frames, frame_samples, d_meta)) return rc > 0 ? 0 : rc;
+    HIP_OK(hipSetDevice(c->device));
+    return compensate_batch_impl(c, d_in, d_out, frames, frame_samples, d_meta, (hipStream_t)stream);
+}
+
+int lphy_hip_compensate_ragged(lphy_hip_ctx* c, const float* d_in, float* d_out, const lphy_ragged_desc* d_desc,
+                               size_t frames, const lphy_frame_meta* d_meta, void* stream) {
+    if (!c) return -EINVAL;
+    if (frames == 0) return 0;
+    if (!d_in || !d_out || !d_desc || !d_meta) return -EINVAL;
+    if (frames > 0x7fffffffULL) return -ERANGE;
+    HIP_OK(hipSetDevice(c->device));
+    return compensate_batch_launch(c, d_in, d_out, CompRagged{d_desc}, frames, kCompRaggedSlots, d_meta,
+                                   (hipStream_t)stream);
 }
 
 int lphy_hip_modulate_batch(lphy_hip_ctx* c, const uint16_t* d_syms, size_t frames,
@@ -1187,6 +1258,33 @@ int lphy_hip_compensate_host(lphy_hip_ctx* c, float* h_iq, size_t count, float c
         return rc;
     }
     HIP_OK(hipMemcpyAsync(h_iq, d, count * sizeof(cf32), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    return 0;
+}
+
+// The batch compensation on host buffers, in place: samples and records in,
+// one launch, samples out; the context's stream and staging (what
+// lphy_hip_ctx_reserve sizes for a demodulation of the same shape holds both).
+int lphy_hip_compensate_batch_host(lphy_hip_ctx* c, float* h_iq, size_t frames, size_t frame_samples,
+                                   const lphy_frame_meta* h_meta) {
+    if (int rc = compensate_batch_check(c, h_iq, h_iq, frames, frame_samples, h_meta)) return rc > 0 ? 0 : rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_OK(hipSetDevice(c->device));
+    const size_t iq_n = frames * frame_samples * sizeof(cf32), meta_n = frames * sizeof(lphy_frame_meta);
+    const size_t o_meta = align_up(iq_n);
+    int rc = ensure_host_stage(c, o_meta + align_up(meta_n));
+    if (rc) return rc;
+    char* base = (char*)c->d_stage;
+    hipStream_t st = c->stream;
+    HIP_OK(hipMemcpyAsync(base, h_iq, iq_n, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(base + o_meta, h_meta, meta_n, hipMemcpyHostToDevice, st));
+    rc = compensate_batch_impl(c, (const float*)base, (float*)base, frames, frame_samples,
+                               (const lphy_frame_meta*)(base + o_meta), st);
+    if (rc) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    HIP_OK(hipMemcpyAsync(h_iq, base, iq_n, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     return 0;
 }

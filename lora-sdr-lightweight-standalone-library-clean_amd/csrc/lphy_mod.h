@@ -4,6 +4,7 @@
 #pragma once
 #include "lphy_args.h"
 #include "libm_exact.h"
+#include "lphy_demod.h"    // (round_to_int)
 #include "lphy_testing.h"  // (the device counter slots)
 
 namespace {
@@ -839,6 +840,136 @@ __global__ void k_comp_shift(cf32* out, const cf32* in, unsigned long long count
     if (n >= count) return;
     const long long src = (long long)n - offset;
     out[n] = (src >= 0 && src < (long long)count) ? in[src] : czero();
+}
+
+// ---------------------------------------------------------------------------
+// compensate_offsets for every frame of a batch in one pass
+// (lphy_hip_compensate_batch / _ragged): frame f rotates by its own
+// meta[f].cfo and shifts by its own meta[f].time_offset, both read here, so
+// an estimate on the same stream feeds it without a host copy.  Rotation and
+// shift fuse into  out[n] = in[n - off] * cis(rate * (n - off))  (0 where
+// n - off leaves the frame): 16 B of traffic per sample and no scratch.
+//
+// The frame geometry is the template argument: CompUniform (frame f at
+// f * frame_samples) or CompRagged (the frame's lphy_ragged_desc).
+//
+// A tile is kCompTile samples: kTile threads x kCompPairs pairs of two
+// samples.  Pairs are cut where the destination is 16-byte aligned (`lead`
+// is 1 when the frame's first output sample is not), so a whole pair goes out
+// in one 16-byte store; the shift makes the source the unaligned side, read
+// with one 16-byte load where its address allows and two 8-byte loads where
+// not.  The frame's first and last sample may form half a pair.
+//
+// Work item w = (frame, slot) = (w / slots, w % slots); a slot takes the
+// frame's tiles slot, slot + slots, ...; the grid strides over the items.
+//   ORDERED = false (out of place): tiles are independent; the uniform form
+//     launches one slot per tile, a flat grid over (frame, tile).
+//   ORDERED = true (in place, out == in): one slot, so one workgroup owns the
+//     frame and walks its tiles in memmove order - descending n for off > 0,
+//     ascending for off < 0 - and per tile loads and rotates the sources into
+//     registers, __syncthreads(), stores.  Why that is enough, for off > 0
+//     (off < 0 mirrors it): tile t stores n in [t*T - lead, (t+1)*T - lead)
+//     and reads n - off; every tile walked after it, t' < t, reads indices
+//     below (t'+1)*T - lead - off <= t*T - lead - off < t*T - lead, the
+//     least index tile t stores, so no store lands on a source still to be
+//     read by a later tile; the sources of tile t itself, which its own
+//     stores may cover when off < T, are all in registers before the barrier
+//     lets any store go.  A frame with off == 0 or no shift is elementwise
+//     (each thread stores what it loaded) and needs no order.  In-place
+//     parallelism is therefore per frame: a batch of many frames fills the
+//     GPU, a single very long buffer is lphy_hip_compensate's case.
+// ---------------------------------------------------------------------------
+constexpr int kCompPairs = 2;
+constexpr int kCompTile = kTile * 2 * kCompPairs;  // samples per tile (1024)
+constexpr unsigned kCompRaggedSlots = 8;           // out of place, ragged: workgroups per frame
+
+struct CompUniform {
+    unsigned long long frame_samples;
+    __device__ __forceinline__ void frame(unsigned long long f, unsigned long long& base,
+                                          unsigned long long& count) const {
+        base = f * frame_samples;
+        count = frame_samples;
+    }
+};
+
+struct CompRagged {
+    const lphy_ragged_desc* __restrict__ desc;  // sym_offset, unit_offset and record [frames] are not read
+    __device__ __forceinline__ void frame(unsigned long long f, unsigned long long& base,
+                                          unsigned long long& count) const {
+        base = desc[f].iq_offset;
+        count = desc[f].samples;
+    }
+};
+
+// samples[src] * complex(cos(ph), sin(ph)), ph = rate * (float)src (phy.cpp:162-165)
+__device__ __forceinline__ cf32 comp_rotate(cf32 x, float rate, long long src) {
+    const float ph = rate * (float)(unsigned long long)src;
+    float sn, cs;
+    lphy_libm::sincosf_exact(ph, &sn, &cs);
+    return cmul_x(x, cf32{cs, sn});
+}
+
+template <class GEO, bool ORDERED>
+__global__ __launch_bounds__(kTile) void k_comp_batch(const cf32* in, cf32* out, GEO geo,
+                                                      const lphy_frame_meta* __restrict__ meta,
+                                                      unsigned long long frames, unsigned slots, int N,
+                                                      int osr) {
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    const unsigned long long work = frames * slots;
+    for (unsigned long long w = blockIdx.x; w < work; w += gridDim.x) {
+        // (everything down to the tile loop is the same in every lane: the
+        // frame's record and descriptor are read once per workgroup)
+        const unsigned long long f = w / slots;
+        unsigned long long base, count;
+        geo.frame(f, base, count);
+        if (count == 0) continue;
+        // phy.cpp:159-160 and :167 as x86-64 evaluates them
+        const float rate = -2.0f * kPi * meta[f].cfo / ((float)N * (float)osr);
+        long long off = round_to_int(meta[f].time_offset);
+        const unsigned long long mag = (unsigned long long)(off < 0 ? -off : off);
+        if (off == (long long)(int)0x80000000u || mag >= count) off = 0;  // phy.cpp:168,173: no shift
+        const cf32* src_fr = in + base;
+        cf32* dst_fr = out + base;
+        const long long lead = (long long)(((unsigned long long)dst_fr >> 3) & 1u);
+        const unsigned long long tiles = (count + (unsigned long long)lead + kCompTile - 1) / kCompTile;
+        for (unsigned long long i = w % slots; i < tiles; i += slots) {
+            const unsigned long long t = (ORDERED && off > 0) ? tiles - 1 - i : i;
+            cf32 v[kCompPairs][2];
+#pragma unroll
+            for (int p = 0; p < kCompPairs; ++p) {
+                const long long n0 = (long long)(t * kCompTile + 2u * (threadIdx.x + (unsigned)p * kTile)) - lead;
+                const long long s0 = n0 - off, s1 = s0 + 1;
+                const bool ok0 = n0 >= 0 && n0 < (long long)count && s0 >= 0 && s0 < (long long)count;
+                const bool ok1 = n0 + 1 < (long long)count && s1 >= 0 && s1 < (long long)count;
+                cf32 x0 = czero(), x1 = czero();
+                if (ok0 && ok1 && (((unsigned long long)(src_fr + s0)) & 15u) == 0) {
+                    const f4 q = *reinterpret_cast<const f4*>(src_fr + s0);
+                    x0 = q.xy;
+                    x1 = q.zw;
+                } else {
+                    if (ok0) x0 = src_fr[s0];
+                    if (ok1) x1 = src_fr[s1];
+                }
+                v[p][0] = ok0 ? comp_rotate(x0, rate, s0) : czero();
+                v[p][1] = ok1 ? comp_rotate(x1, rate, s1) : czero();
+            }
+            if (ORDERED) __syncthreads();
+#pragma unroll
+            for (int p = 0; p < kCompPairs; ++p) {
+                const long long n0 = (long long)(t * kCompTile + 2u * (threadIdx.x + (unsigned)p * kTile)) - lead;
+                const bool w0 = n0 >= 0 && n0 < (long long)count, w1 = n0 + 1 < (long long)count;
+                if (w0 && w1) {
+                    f4 q;
+                    q.xy = v[p][0];
+                    q.zw = v[p][1];
+                    *reinterpret_cast<f4*>(dst_fr + n0) = q;
+                } else {
+                    if (w0) dst_fr[n0] = v[p][0];
+                    if (w1) dst_fr[n0 + 1] = v[p][1];
+                }
+            }
+        }
+    }
 }
 
 }  // namespace

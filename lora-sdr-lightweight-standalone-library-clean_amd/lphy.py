@@ -108,6 +108,7 @@ EXPORTS = (
     "lphy_hip_lorawan_mic_host",
     "lphy_hip_ragged_layout", "lphy_hip_demod_ragged", "lphy_hip_demod_ragged_host",
     "lphy_hip_detect_batch", "lphy_hip_detect_host", "lphy_hip_detect_serial_count",
+    "lphy_hip_compensate_batch", "lphy_hip_compensate_ragged", "lphy_hip_compensate_batch_host",
 )
 
 WHITEN_SX1232, WHITEN_SX1272, WHITEN_SX1272_LFSR = 0, 1, 2
@@ -170,6 +171,9 @@ def load(path: Path | None = None) -> C.CDLL:
     L.lphy_hip_decode_batch.argtypes = [_vp, _vp, _sz, _sz, _vp, _vp, _vp]
     L.lphy_hip_estimate_batch.argtypes = [_vp, _vp, _sz, _sz, _sz, _vp, _vp]
     L.lphy_hip_compensate.argtypes = [_vp, _vp, _sz, C.c_float, C.c_float, _vp]
+    L.lphy_hip_compensate_batch.argtypes = [_vp, _vp, _vp, _sz, _sz, _vp, _vp]
+    L.lphy_hip_compensate_ragged.argtypes = [_vp, _vp, _vp, _vp, _sz, _vp, _vp]
+    L.lphy_hip_compensate_batch_host.argtypes = [_vp, _vp, _sz, _sz, _vp]
     L.lphy_hip_modulate_batch.argtypes = [_vp, _vp, _sz, _sz, _vp, C.c_float, C.c_uint8, _vp]
     L.lphy_hip_demod_host.argtypes = [_vp, _vp, _sz, _sz, _vp, _vp, _vp, C.c_int, C.c_uint]
     L.lphy_hip_decode_host.argtypes = [_vp, _vp, _sz, _vp, _vp]
@@ -397,6 +401,32 @@ class Demodulator:
                                               p_meta, stream),
              "lphy_hip_estimate_batch")
 
+    def compensate_batch(self, iq_in, iq_out, frames, frame_samples, meta, stream=None):
+        """compensate_offsets on each of `frames` device frames with the frame's
+        own meta[f].cfo / .time_offset, read on the device
+        (lphy_hip_compensate_batch).  iq_out may be iq_in (in place) or a
+        disjoint tensor; `meta` is not written.  Asynchronous."""
+        dv = self.device
+        p_in = _dev_buf(iq_in, "iq_in", dv, frames * frame_samples * 8, None)
+        p_out = _dev_buf(iq_out, "iq_out", dv, frames * frame_samples * 8, None)
+        p_meta = _dev_buf(meta, "meta", dv, frames * 32, None)
+        _chk(self.lib.lphy_hip_compensate_batch(self.ctx, p_in, p_out, frames, frame_samples, p_meta,
+                                                stream), "lphy_hip_compensate_batch")
+
+    def compensate_ragged(self, iq_in, iq_out, desc, frames, meta, stream=None, iq_samples=None):
+        """The same for frames of different lengths: frame f is
+        desc[f]["samples"] samples at desc[f]["iq_offset"] in iq_in and iq_out
+        alike (`desc`: device tensor of RAGGED_DESC_DTYPE records; record
+        [frames] is not read).  iq_samples: the extent the descriptors span
+        (checked against the tensors)."""
+        dv = self.device
+        p_in = _dev_buf(iq_in, "iq_in", dv, (iq_samples or 0) * 8, None)
+        p_out = _dev_buf(iq_out, "iq_out", dv, (iq_samples or 0) * 8, None)
+        p_desc = _dev_buf(desc, "desc", dv, frames * 32, None)
+        p_meta = _dev_buf(meta, "meta", dv, frames * 32, None)
+        _chk(self.lib.lphy_hip_compensate_ragged(self.ctx, p_in, p_out, p_desc, frames, p_meta, stream),
+             "lphy_hip_compensate_ragged")
+
     # --- streaming ingestion (lphy_hip_demod_stream) --------------------
     def demod_stream(self, fd: int, frame_samples: int, mode: int, flags: int = 0,
                      chunk_frames: int = 0, max_frames: int = 0, capacity: int = 0):
@@ -458,6 +488,19 @@ class Demodulator:
         x = np.array(iq, np.complex64, copy=True).reshape(-1)
         _chk(self.lib.lphy_hip_compensate_host(self.ctx, x.ctypes.data, x.size, cfo,
                                                time_offset), "lphy_hip_compensate_host")
+        return x
+
+    def compensate_batch_host(self, iq: np.ndarray, frames: int, frame_samples: int, meta: np.ndarray):
+        """compensate_batch on host samples; `meta`: `frames` META_DTYPE
+        records (cfo and time_offset are read).  Returns the corrected copy."""
+        x = np.array(iq, np.complex64, copy=True).reshape(-1)
+        m = np.ascontiguousarray(meta, META_DTYPE).reshape(-1)
+        if x.size != frames * frame_samples or m.size != frames:
+            raise ValueError(f"iq: {x.size} samples, meta: {m.size} records for {frames} x {frame_samples}")
+        pad = np.zeros(1, np.complex64)
+        _chk(self.lib.lphy_hip_compensate_batch_host(self.ctx, (x if x.size else pad).ctypes.data, frames,
+                                                     frame_samples, m.ctypes.data if m.size else None),
+             "lphy_hip_compensate_batch_host")
         return x
 
     def modulate_host(self, syms: np.ndarray, amplitude=1.0, sync=0x12):
