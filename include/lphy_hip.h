@@ -123,6 +123,8 @@ int lphy_hip_ctx_share(lphy_hip_ctx** out, const lphy_hip_ctx* base, unsigned os
  * of `frame_samples` samples (the *_host entry points below), so that those
  * calls allocate nothing: the reference allocates nothing after init
  * (API_SPEC.md:9-14; lora_demod_init's max_samples, LoRaDemod.cpp:11-33).
+ * The size covers every *_host form at that shape: frames of frame_samples
+ * each, or one buffer of frames * frame_samples samples.
  * A larger call later grows the staging once.  Returns 0 or -ENOMEM/-EIO. */
 int lphy_hip_ctx_reserve(lphy_hip_ctx* ctx, size_t frames, size_t frame_samples);
 

@@ -3,12 +3,13 @@
 // kernels (lphy_route.h) and their launch through the per-SF tables (SfOps:
 // the kernels templated on SF are the lphy_sf.hip objects'), and the
 // SF-independent kernels themselves: the finalisation (k_finalize), the
-// modulator and the compensation (lphy_mod.h), k_mark_recheck.
+// modulator and the compensation (lphy_mod.h), k_mark_recheck.  The host-
+// buffer forms (*_host) are lphy_host.h, included at the end.
 #include "lphy_args.h"
 #include "lphy_final.h"
 #include "lphy_mod.h"
-#include "lphy_ragged_layout.h"
 #include "lphy_route.h"
+#include "lphy_stage_plan.h"
 #include "lphy_testing.h"
 
 #include <cmath>
@@ -53,6 +54,8 @@ struct lphy_tables {
     }
 };
 
+constexpr size_t kPinnedMax = size_t(32) << 20;
+
 struct lphy_hip_ctx {
     int device = 0;
     unsigned sf = 0, N = 0, bw_hz = 0, osr = 1;
@@ -85,6 +88,7 @@ struct lphy_hip_ctx {
     // per-SF crossover, fused_min_frames; lphy_hip_ctx_set_fused_min_frames)
     std::atomic<long> fused_min{-1};
     std::atomic<int> mod_force_serial{0};  // (test build: lphy_hip_test_mod_force_serial)
+    std::atomic<size_t> pinned_max{kPinnedMax};  // (test build: lphy_hip_test_pinned_max)
     // (per-call scratch of the device entry points - the SF 11-12 speculation
     // records, the producer's phases, the compensation's shift buffer - comes
     // from the stream-ordered allocator on the caller's stream, so concurrent
@@ -184,8 +188,6 @@ size_t fused_min_frames(const lphy_hip_ctx* c) {
     return t[c->sf <= 12 ? c->sf : 12];
 }
 
-constexpr size_t kPinnedMax = size_t(32) << 20;
-
 int ensure_stage(lphy_hip_ctx* c, size_t bytes) {
     if (c->stage_bytes >= bytes) return 0;
     void* old = c->d_stage;
@@ -204,8 +206,6 @@ int ensure_stage(lphy_hip_ctx* c, size_t bytes) {
     }
     return 0;
 }
-
-size_t align_up(size_t x) { return (x + 255) & ~size_t(255); }
 
 // Per-call device scratch of the device-buffer entry points, one policy for
 // all of them (demod_batch's SF 11-12 speculation records, the producer's
@@ -246,6 +246,27 @@ struct StreamScratch {
         }
     }
 };
+
+// The fields of DemodArgs / DetectArgs that come from the context alone.
+template <class ARGS>
+void ctx_args(const lphy_hip_ctx* c, ARGS& A) {
+    A.tw = c->d_tw;
+    A.down = c->d_down;
+    A.win = c->window == LPHY_WINDOW_HANN ? c->d_win : nullptr;
+    A.power_scale = c->power_scale;
+    A.counters = c->d_counters;
+}
+
+// Counters [first, first + n) of the context after everything on the device
+// is done, cleared with `reset`.
+int read_counters(lphy_hip_ctx* c, int first, int n, unsigned long long* out, int reset) {
+    if (!c || !out) return -EINVAL;
+    HIP_OK(hipSetDevice(c->device));
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(out, c->d_counters + first, n * sizeof(*out), hipMemcpyDeviceToHost));
+    if (reset) HIP_OK(hipMemset(c->d_counters + first, 0, n * sizeof(*out)));
+    return 0;
+}
 
 }  // namespace
 
@@ -439,10 +460,8 @@ int demod_batch_impl(lphy_hip_ctx* c, const float* d_iq, size_t frames, size_t f
     if (mode == LPHY_MODE_DECHIRP_LORA_DEMODULATE && (c->osr != 1 || frame_samples % c->N)) return -EINVAL;
     HIP_OK(hipSetDevice(c->device));
     DemodArgs A{};
+    ctx_args(c, A);
     A.iq = reinterpret_cast<const cf32*>(d_iq);
-    A.tw = c->d_tw;
-    A.down = c->d_down;
-    A.win = c->window == LPHY_WINDOW_HANN ? c->d_win : nullptr;
     A.syms = d_syms;
     A.meta = d_meta;
     A.frames = frames;
@@ -450,11 +469,9 @@ int demod_batch_impl(lphy_hip_ctx* c, const float* d_iq, size_t frames, size_t f
     A.total_syms = total;
     A.out_per_frame = lphy_hip_syms_per_frame(c, frame_samples, mode);
     A.osr = (int)c->osr;
-    A.power_scale = c->power_scale;
     A.mode = mode;
     A.no_scratch = (flags & LPHY_F_NO_SCRATCH) ? 1 : 0;
     A.exact_rotation = (flags & LPHY_F_EXACT_ROTATION) ? 1 : 0;
-    A.counters = c->d_counters;
     A.spec = (mode != LPHY_MODE_DEMODULATE && !A.no_scratch && !(flags & LPHY_F_SCAN_FIRST)) ? 1 : 0;
     A.debug_recheck = (flags & LPHY_F_DEBUG_RECHECK) ? 1 : 0;
     const size_t est_syms = mode == LPHY_MODE_DEMODULATE ? 2 : (total < 2 ? total : 2);
@@ -537,19 +554,15 @@ int demod_ragged_impl(lphy_hip_ctx* c, const float* d_iq, const lphy_ragged_desc
     HIP_OK(hipSetDevice(c->device));
     RaggedArgs R{};
     DemodArgs& A = R.A;
+    ctx_args(c, A);
     A.iq = reinterpret_cast<const cf32*>(d_iq);
-    A.tw = c->d_tw;
-    A.down = c->d_down;
-    A.win = c->window == LPHY_WINDOW_HANN ? c->d_win : nullptr;
     A.syms = d_syms;
     A.meta = d_meta;
     A.frames = frames;
     A.osr = 1;
-    A.power_scale = c->power_scale;
     A.mode = mode;
     A.no_scratch = (flags & LPHY_F_NO_SCRATCH) ? 1 : 0;
     A.exact_rotation = 1;
-    A.counters = c->d_counters;
     R.desc = d_desc;
     R.bytes = (flags & LPHY_F_DECODE) ? d_bytes : nullptr;
     R.units_hint = units_hint;
@@ -593,10 +606,8 @@ int detect_impl(lphy_hip_ctx* c, const float* d_iq, size_t total_samples, size_t
     if (!ops || !ops->detect) return -ENOTSUP;  // (an experiment build without this SF's object)
     HIP_OK(hipSetDevice(c->device));
     DetectArgs D{};
+    ctx_args(c, D);
     D.iq = reinterpret_cast<const cf32*>(d_iq);
-    D.tw = c->d_tw;
-    D.down = c->d_down;
-    D.win = c->window == LPHY_WINDOW_HANN ? c->d_win : nullptr;
     D.out = d_out;
     D.total_samples = total_samples;
     D.first = first;
@@ -604,8 +615,6 @@ int detect_impl(lphy_hip_ctx* c, const float* d_iq, size_t total_samples, size_t
     D.step = step;
     D.windows = windows;
     D.dechirp = (flags & LPHY_DET_DECHIRP) ? 1 : 0;
-    D.power_scale = c->power_scale;
-    D.counters = c->d_counters;
     return ops->detect(D, st);
 }
 }  // namespace
@@ -619,23 +628,13 @@ int lphy_hip_detect_batch(lphy_hip_ctx* c, const float* d_iq, size_t total_sampl
 }
 
 int lphy_hip_detect_serial_count(lphy_hip_ctx* c, unsigned long long* out, int reset) {
-    if (!c || !out) return -EINVAL;
-    HIP_OK(hipSetDevice(c->device));
-    HIP_OK(hipDeviceSynchronize());
-    HIP_OK(hipMemcpy(out, c->d_counters + kCtrDetectSerial, sizeof(*out), hipMemcpyDeviceToHost));
-    if (reset) HIP_OK(hipMemset(c->d_counters + kCtrDetectSerial, 0, sizeof(*out)));
-    return 0;
+    return read_counters(c, kCtrDetectSerial, 1, out, reset);
 }
 
 #ifdef LPHY_PROFILE_PHASES
 // experiments only: read and clear the kernels' per-phase clock sums (8)
 int lphy_hip_phase_cycles(lphy_hip_ctx* c, unsigned long long* out8) {
-    if (!c || !out8) return -EINVAL;
-    HIP_OK(hipSetDevice(c->device));
-    HIP_OK(hipDeviceSynchronize());
-    HIP_OK(hipMemcpy(out8, c->d_counters + kCtrClocks, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    HIP_OK(hipMemset(c->d_counters + kCtrClocks, 0, 8 * sizeof(unsigned long long)));
-    return 0;
+    return read_counters(c, kCtrClocks, 8, out8, 1);
 }
 #endif
 
@@ -675,19 +674,15 @@ int lphy_hip_estimate_batch(lphy_hip_ctx* c, const float* d_iq, size_t frames,
     if (syms * c->osr > 0x7fffffffULL) return -ERANGE;
     HIP_OK(hipSetDevice(c->device));
     DemodArgs A{};
+    ctx_args(c, A);
     A.iq = reinterpret_cast<const cf32*>(d_iq);
-    A.tw = c->d_tw;
-    A.down = c->d_down;
-    A.win = c->window == LPHY_WINDOW_HANN ? c->d_win : nullptr;
     A.meta = d_meta;
     A.frames = frames;
     A.frame_samples = frame_samples;
     A.total_syms = frame_samples / step;
     A.osr = (int)c->osr;
-    A.power_scale = c->power_scale;
     A.mode = LPHY_MODE_DEMODULATE;
     A.est_units = (int)(syms * c->osr);
-    A.counters = c->d_counters;
     const SfOps* o = sf_ops(c->sf);
     return o ? o->estimate(A, (hipStream_t)stream) : -EINVAL;
 }
@@ -813,7 +808,10 @@ size_t mod_scratch_bytes(const lphy_hip_ctx* c, size_t frames, size_t nsyms) {
 const ModFastLimits& mod_fast_limits(int device) {
     static ModFastLimits lim[64];
     static std::once_flag once[64];
-    const int d = device >= 0 && device < 64 ? device : 0;
+    // (a device past the table: the limit no attribute has to be raised for)
+    static const ModFastLimits unraised{size_t(64) << 10};
+    if (device < 0 || device >= 64) return unraised;
+    const int d = device;
     std::call_once(once[d], [d] {
         int cur = 0, per_block = 0;
         (void)hipGetDevice(&cur);
@@ -943,12 +941,7 @@ int lphy_hip_sync(void* stream) {
 }
 
 int lphy_hip_recheck_count(lphy_hip_ctx* c, unsigned long long* out, int reset) {
-    if (!c || !out) return -EINVAL;
-    HIP_OK(hipSetDevice(c->device));
-    HIP_OK(hipDeviceSynchronize());
-    HIP_OK(hipMemcpy(out, c->d_counters + kCtrRecheck, sizeof(*out), hipMemcpyDeviceToHost));
-    if (reset) HIP_OK(hipMemset(c->d_counters + kCtrRecheck, 0, sizeof(*out)));
-    return 0;
+    return read_counters(c, kCtrRecheck, 1, out, reset);
 }
 
 #ifdef LPHY_TEST_PATHS
@@ -963,13 +956,18 @@ int lphy_hip_test_mod_force_serial(lphy_hip_ctx* c, int on) {
     return 0;
 }
 
-int lphy_hip_test_counter(lphy_hip_ctx* c, int idx, unsigned long long* out, int reset) {
-    if (!c || !out || idx < 0 || idx >= kCounters) return -EINVAL;
-    HIP_OK(hipSetDevice(c->device));
-    HIP_OK(hipDeviceSynchronize());
-    HIP_OK(hipMemcpy(out, c->d_counters + idx, sizeof(*out), hipMemcpyDeviceToHost));
-    if (reset) HIP_OK(hipMemset(c->d_counters + idx, 0, sizeof(*out)));
+// Test build only: the largest call (its copied slices) that goes through the
+// pinned mirror on this context; 0 sends every *_host call down the pageable
+// path, which otherwise needs a call above kPinnedMax (lphy_host.h).
+int lphy_hip_test_pinned_max(lphy_hip_ctx* c, size_t bytes) {
+    if (!c) return -EINVAL;
+    c->pinned_max.store(bytes, std::memory_order_relaxed);
     return 0;
+}
+
+int lphy_hip_test_counter(lphy_hip_ctx* c, int idx, unsigned long long* out, int reset) {
+    if (idx < 0 || idx >= kCounters) return -EINVAL;
+    return read_counters(c, idx, 1, out, reset);
 }
 #endif
 
@@ -995,330 +993,6 @@ int lphy_hip_bounds_violations(lphy_hip_ctx* c, unsigned long long* out, int res
 #endif
 }
 
-// ---- host-buffer convenience (synchronous) --------------------------------
-// Each call runs on the context's own stream and waits for that stream only:
-// host copies in (async, ordered on the stream), the kernels, host copies
-// out, hipStreamSynchronize.  Staging comes from lphy_hip_ctx_reserve; a
-// call larger than the reservation grows it (the only allocation after it).
-namespace {
-struct HostLayout {  // byte offsets in the staging buffer of one *_host call
-    size_t iq = 0, syms = 0, bytes = 0, meta = 0, spec = 0, end = 0;
-};
-
-HostLayout demod_layout(const lphy_hip_ctx* c, size_t frames, size_t frame_samples, int mode) {
-    const size_t per = lphy_hip_syms_per_frame(c, frame_samples, mode);
-    HostLayout L;
-    L.syms = align_up(frames * frame_samples * sizeof(cf32));
-    L.bytes = L.syms + align_up(std::max<size_t>(1, frames * per) * sizeof(uint16_t));
-    L.meta = L.bytes + align_up(std::max<size_t>(1, frames * (per / 2)));
-    L.spec = L.meta + align_up(frames * sizeof(lphy_frame_meta));
-    L.end = L.spec + align_up(frames * sizeof(uint4));
-    return L;
-}
-
-// staging every *_host entry point needs for calls of up to `frames`
-// frames of `frame_samples` samples (or one buffer of frames * frame_samples)
-size_t host_stage_bytes(const lphy_hip_ctx* c, size_t frames, size_t frame_samples) {
-    const size_t n = frames * frame_samples;
-    const size_t syms = frame_samples / ((size_t)c->N * c->osr) + 2;
-    size_t b = std::max(demod_layout(c, frames, frame_samples, LPHY_MODE_LORA_DEMODULATE).end,
-                        demod_layout(c, frames, frame_samples, LPHY_MODE_DEMODULATE).end);
-    b = std::max(b, 2 * align_up(n * sizeof(cf32)));                                      // compensate
-    b = std::max(b, align_up(syms * sizeof(uint16_t)) + align_up(n * sizeof(cf32)) +
-                        mod_scratch_bytes(c, 1, syms - 2));                               // modulate
-    b = std::max(b, 3 * align_up(std::max<size_t>(1, frames * syms) * sizeof(uint16_t)));  // decode
-    return b;
-}
-
-int ensure_host_stage(lphy_hip_ctx* c, size_t bytes) {
-    if (c->stage_bytes >= bytes) return 0;
-    // the old staging may still be read by this context's stream
-    if (c->d_stage) HIP_OK(hipStreamSynchronize(c->stream));
-    return ensure_stage(c, bytes);
-}
-}  // namespace
-
-int lphy_hip_ctx_reserve(lphy_hip_ctx* c, size_t frames, size_t frame_samples) {
-    if (!c) return -EINVAL;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_OK(hipSetDevice(c->device));
-    return ensure_host_stage(c, host_stage_bytes(c, std::max<size_t>(frames, 1), frame_samples));
-}
-
-int lphy_hip_demod_host(lphy_hip_ctx* c, const float* h_iq, size_t frames,
-                        size_t frame_samples, uint16_t* h_syms, uint8_t* h_bytes,
-                        lphy_frame_meta* h_meta, int mode, unsigned flags) {
-    if (!c || !h_iq || !h_meta) return -EINVAL;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_OK(hipSetDevice(c->device));
-    const size_t per = lphy_hip_syms_per_frame(c, frame_samples, mode);
-    const HostLayout L = demod_layout(c, frames, frame_samples, mode);
-    int rc = ensure_host_stage(c, L.end);
-    if (rc) return rc;
-    char* base = (char*)c->d_stage;
-    float* d_iq = (float*)(base + L.iq);
-    uint16_t* d_syms = (uint16_t*)(base + L.syms);
-    uint8_t* d_bytes = (uint8_t*)(base + L.bytes);
-    lphy_frame_meta* d_meta = (lphy_frame_meta*)(base + L.meta);
-    hipStream_t st = c->stream;
-    const size_t iq_n = frames * frame_samples * sizeof(cf32), meta_n = frames * sizeof(lphy_frame_meta);
-    const size_t syms_n = frames * per * sizeof(uint16_t), bytes_n = frames * (per / 2);
-    const bool decode = (flags & LPHY_F_DECODE) != 0;
-    // pinned: IQ and the zeroed records in with one copy, symbols / bytes /
-    // records out with one
-    char* h = L.spec <= c->h_stage_bytes ? (char*)c->h_stage : nullptr;
-    if (h) {
-        std::memcpy(h + L.iq, h_iq, iq_n);
-        std::memset(h + L.meta, 0, meta_n);
-        HIP_OK(hipMemcpyAsync(base, h, L.spec, hipMemcpyHostToDevice, st));
-    } else {
-        HIP_OK(hipMemcpyAsync(d_iq, h_iq, iq_n, hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemsetAsync(d_meta, 0, meta_n, st));
-    }
-    rc = demod_batch_impl(c, d_iq, frames, frame_samples, d_syms, decode ? d_bytes : nullptr, d_meta, mode, flags,
-                          st, base + L.spec);
-    if (rc) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    if (h) {
-        HIP_OK(hipMemcpyAsync(h + L.syms, base + L.syms, L.spec - L.syms, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
-        std::memcpy(h_meta, h + L.meta, meta_n);
-        if (h_syms && per) std::memcpy(h_syms, h + L.syms, syms_n);
-        if (h_bytes && decode && per / 2) std::memcpy(h_bytes, h + L.bytes, bytes_n);
-        return 0;
-    }
-    HIP_OK(hipMemcpyAsync(h_meta, d_meta, meta_n, hipMemcpyDeviceToHost, st));
-    if (h_syms && per) HIP_OK(hipMemcpyAsync(h_syms, d_syms, syms_n, hipMemcpyDeviceToHost, st));
-    if (h_bytes && decode && per / 2) HIP_OK(hipMemcpyAsync(h_bytes, d_bytes, bytes_n, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    return 0;
-}
-
-// The ragged call on host buffers: IQ, descriptors and the caller's output
-// slots in (slots no frame owns come back as they went), the three launches,
-// symbols / bytes / records out; the context's stream and staging.
-int lphy_hip_demod_ragged_host(lphy_hip_ctx* c, const float* h_iq, const lphy_ragged_desc* h_desc, size_t frames,
-                               uint16_t* h_syms, uint8_t* h_bytes, lphy_frame_meta* h_meta, int mode,
-                               unsigned flags) {
-    if (!c || !h_desc || !h_meta) return -EINVAL;
-    if (mode < 0 || mode > 2) return -EINVAL;
-    if (flags & ~(unsigned)(LPHY_F_DECODE | LPHY_F_NO_SCRATCH)) return -ENOTSUP;
-    if (c->osr != 1 || c->sf < 7) return -ENOTSUP;
-    const bool decode = (flags & LPHY_F_DECODE) != 0;
-    if (decode && !h_bytes) return -EINVAL;
-    if (frames == 0) return 0;
-    if (frames > 0x7fffffffULL) return -ERANGE;
-    uint64_t iq_samples = 0, out_syms = 0;
-    if (int rc = ragged_extent(c->N, h_desc, frames, mode, &iq_samples, &out_syms)) return rc;
-    if ((iq_samples && !h_iq) || (out_syms && !h_syms)) return -EINVAL;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_OK(hipSetDevice(c->device));
-    const size_t iq_n = (size_t)iq_samples * sizeof(cf32), desc_n = (frames + 1) * sizeof(lphy_ragged_desc);
-    const size_t syms_n = (size_t)out_syms * sizeof(uint16_t), bytes_n = (size_t)(out_syms + 1) / 2;
-    const size_t meta_n = frames * sizeof(lphy_frame_meta);
-    const size_t o_desc = align_up(std::max<size_t>(1, iq_n)), o_syms = o_desc + align_up(desc_n);
-    const size_t o_bytes = o_syms + align_up(std::max<size_t>(1, syms_n));
-    const size_t o_meta = o_bytes + align_up(std::max<size_t>(1, bytes_n));
-    int rc = ensure_host_stage(c, o_meta + align_up(meta_n));
-    if (rc) return rc;
-    char* base = (char*)c->d_stage;
-    hipStream_t st = c->stream;
-    if (iq_n) HIP_OK(hipMemcpyAsync(base, h_iq, iq_n, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(base + o_desc, h_desc, desc_n, hipMemcpyHostToDevice, st));
-    if (syms_n) HIP_OK(hipMemcpyAsync(base + o_syms, h_syms, syms_n, hipMemcpyHostToDevice, st));
-    if (decode && bytes_n) HIP_OK(hipMemcpyAsync(base + o_bytes, h_bytes, bytes_n, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemsetAsync(base + o_meta, 0, meta_n, st));
-    rc = demod_ragged_impl(c, (const float*)base, (const lphy_ragged_desc*)(base + o_desc), frames,
-                           (uint16_t*)(base + o_syms), decode ? (uint8_t*)(base + o_bytes) : nullptr,
-                           (lphy_frame_meta*)(base + o_meta), mode, flags, st, h_desc[frames].unit_offset);
-    if (rc) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    HIP_OK(hipMemcpyAsync(h_meta, base + o_meta, meta_n, hipMemcpyDeviceToHost, st));
-    if (syms_n) HIP_OK(hipMemcpyAsync(h_syms, base + o_syms, syms_n, hipMemcpyDeviceToHost, st));
-    if (decode && bytes_n) HIP_OK(hipMemcpyAsync(h_bytes, base + o_bytes, bytes_n, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    return 0;
-}
-
-// The detector on host buffers: the samples the windows span in (h_iq[first
-// .. last]), one launch, the records out; the context's stream and staging.
-int lphy_hip_detect_host(lphy_hip_ctx* c, const float* h_iq, size_t total_samples, size_t first, size_t hop,
-                         size_t step, size_t windows, lphy_detect_rec* h_out, unsigned flags) {
-    size_t last = 0;
-    if (int rc = detect_check(c, h_iq, total_samples, first, hop, step, windows, h_out, flags, &last))
-        return rc > 0 ? 0 : rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_OK(hipSetDevice(c->device));
-    const size_t span = last - first + 1;
-    const size_t iq_n = span * sizeof(cf32), out_n = windows * sizeof(lphy_detect_rec);
-    const size_t o_out = align_up(iq_n);
-    int rc = ensure_host_stage(c, o_out + align_up(out_n));
-    if (rc) return rc;
-    char* base = (char*)c->d_stage;
-    hipStream_t st = c->stream;
-    HIP_OK(hipMemcpyAsync(base, h_iq + 2 * first, iq_n, hipMemcpyHostToDevice, st));
-    rc = detect_impl(c, (const float*)base, span, 0, hop, step, windows, (lphy_detect_rec*)(base + o_out), flags, st);
-    if (rc) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    HIP_OK(hipMemcpyAsync(h_out, base + o_out, out_n, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    return 0;
-}
-
-int lphy_hip_decode_host(lphy_hip_ctx* c, const uint16_t* h_syms, size_t count,
-                         uint8_t* h_bytes, lphy_frame_meta* h_meta) {
-    if (!c || !h_syms || !h_bytes || !h_meta) return -EINVAL;
-    if (count & 1) return -EINVAL;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_OK(hipSetDevice(c->device));
-    const size_t sym_b = align_up(std::max<size_t>(1, count) * sizeof(uint16_t));
-    const size_t byte_b = align_up(std::max<size_t>(1, count / 2));
-    const size_t meta_b = align_up(sizeof(lphy_frame_meta));
-    int rc = ensure_host_stage(c, sym_b + byte_b + meta_b);
-    if (rc) return rc;
-    char* base = (char*)c->d_stage;
-    uint16_t* d_syms = (uint16_t*)base;
-    uint8_t* d_bytes = (uint8_t*)(base + sym_b);
-    lphy_frame_meta* d_meta = (lphy_frame_meta*)(base + sym_b + byte_b);
-    hipStream_t st = c->stream;
-    const size_t end = sym_b + byte_b + meta_b;
-    char* h = end <= c->h_stage_bytes ? (char*)c->h_stage : nullptr;
-    if (h) {  // pinned: symbols and the zeroed record in, bytes and record out
-        if (count) std::memcpy(h, h_syms, count * sizeof(uint16_t));
-        std::memset(h + sym_b + byte_b, 0, sizeof(lphy_frame_meta));
-        HIP_OK(hipMemcpyAsync(base, h, end, hipMemcpyHostToDevice, st));
-    } else {
-        if (count) HIP_OK(hipMemcpyAsync(d_syms, h_syms, count * sizeof(uint16_t), hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemsetAsync(d_meta, 0, sizeof(lphy_frame_meta), st));
-    }
-    rc = lphy_hip_decode_batch(c, d_syms, 1, count, d_bytes, d_meta, st);
-    if (rc) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    if (h) {
-        HIP_OK(hipMemcpyAsync(h + sym_b, base + sym_b, byte_b + meta_b, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
-        std::memcpy(h_meta, h + sym_b + byte_b, sizeof(lphy_frame_meta));
-        if (count / 2) std::memcpy(h_bytes, h + sym_b, count / 2);
-        return 0;
-    }
-    HIP_OK(hipMemcpyAsync(h_meta, d_meta, sizeof(lphy_frame_meta), hipMemcpyDeviceToHost, st));
-    if (count / 2) HIP_OK(hipMemcpyAsync(h_bytes, d_bytes, count / 2, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    return 0;
-}
-
-int lphy_hip_estimate_host(lphy_hip_ctx* c, const float* h_iq, size_t count,
-                           lphy_frame_meta* h_meta) {
-    if (!c || !h_iq || !h_meta) return -EINVAL;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_OK(hipSetDevice(c->device));
-    const size_t iq_b = align_up(std::max<size_t>(1, count) * sizeof(cf32));
-    const size_t meta_b = align_up(sizeof(lphy_frame_meta));
-    int rc = ensure_host_stage(c, iq_b + meta_b);
-    if (rc) return rc;
-    char* base = (char*)c->d_stage;
-    float* d_iq = (float*)base;
-    lphy_frame_meta* d_meta = (lphy_frame_meta*)(base + iq_b);
-    hipStream_t st = c->stream;
-    HIP_OK(hipMemcpyAsync(d_iq, h_iq, count * sizeof(cf32), hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_meta, h_meta, sizeof(lphy_frame_meta), hipMemcpyHostToDevice, st));
-    rc = lphy_hip_estimate_batch(c, d_iq, 1, count, count, d_meta, st);
-    if (rc) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    HIP_OK(hipMemcpyAsync(h_meta, d_meta, sizeof(lphy_frame_meta), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    return 0;
-}
-
-int lphy_hip_compensate_host(lphy_hip_ctx* c, float* h_iq, size_t count, float cfo,
-                             float time_offset) {
-    if (!c || !h_iq) return -EINVAL;
-    if (count == 0) return 0;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_OK(hipSetDevice(c->device));
-    const size_t iq_b = align_up(count * sizeof(cf32));
-    int rc = ensure_host_stage(c, 2 * iq_b);
-    if (rc) return rc;
-    float* d = (float*)c->d_stage;
-    hipStream_t st = c->stream;
-    HIP_OK(hipMemcpyAsync(d, h_iq, count * sizeof(cf32), hipMemcpyHostToDevice, st));
-    rc = compensate_impl(c, d, count, cfo, time_offset, st, (char*)c->d_stage + iq_b);
-    if (rc) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    HIP_OK(hipMemcpyAsync(h_iq, d, count * sizeof(cf32), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    return 0;
-}
-
-// The batch compensation on host buffers, in place: samples and records in,
-// one launch, samples out; the context's stream and staging (what
-// lphy_hip_ctx_reserve sizes for a demodulation of the same shape holds both).
-int lphy_hip_compensate_batch_host(lphy_hip_ctx* c, float* h_iq, size_t frames, size_t frame_samples,
-                                   const lphy_frame_meta* h_meta) {
-    if (int rc = compensate_batch_check(c, h_iq, h_iq, frames, frame_samples, h_meta)) return rc > 0 ? 0 : rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_OK(hipSetDevice(c->device));
-    const size_t iq_n = frames * frame_samples * sizeof(cf32), meta_n = frames * sizeof(lphy_frame_meta);
-    const size_t o_meta = align_up(iq_n);
-    int rc = ensure_host_stage(c, o_meta + align_up(meta_n));
-    if (rc) return rc;
-    char* base = (char*)c->d_stage;
-    hipStream_t st = c->stream;
-    HIP_OK(hipMemcpyAsync(base, h_iq, iq_n, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(base + o_meta, h_meta, meta_n, hipMemcpyHostToDevice, st));
-    rc = compensate_batch_impl(c, (const float*)base, (float*)base, frames, frame_samples,
-                               (const lphy_frame_meta*)(base + o_meta), st);
-    if (rc) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    HIP_OK(hipMemcpyAsync(h_iq, base, iq_n, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    return 0;
-}
-
-int lphy_hip_modulate_host(lphy_hip_ctx* c, const uint16_t* h_syms, size_t nsyms,
-                           float* h_iq, float amplitude, uint8_t sync) {
-    if (!c || !h_iq || (nsyms && !h_syms)) return -EINVAL;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_OK(hipSetDevice(c->device));
-    const size_t samples = (nsyms + 2) * (size_t)c->N * c->osr;
-    const size_t sym_b = align_up(std::max<size_t>(1, nsyms) * sizeof(uint16_t));
-    const size_t iq_b = align_up(samples * sizeof(cf32));
-    int rc = ensure_host_stage(c, sym_b + iq_b + mod_scratch_bytes(c, 1, nsyms));
-    if (rc) return rc;
-    char* base = (char*)c->d_stage;
-    uint16_t* d_syms = (uint16_t*)base;
-    float* d_iq = (float*)(base + sym_b);
-    hipStream_t st = c->stream;
-    char* h = sym_b + iq_b <= c->h_stage_bytes ? (char*)c->h_stage : nullptr;
-    if (nsyms) {
-        if (h) std::memcpy(h, h_syms, nsyms * sizeof(uint16_t));
-        HIP_OK(hipMemcpyAsync(d_syms, h ? (const void*)h : (const void*)h_syms, nsyms * sizeof(uint16_t),
-                              hipMemcpyHostToDevice, st));
-    }
-    rc = modulate_impl(c, d_syms, 1, nsyms, d_iq, amplitude, sync, st, base + sym_b + iq_b);
-    if (rc) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    HIP_OK(hipMemcpyAsync(h ? (void*)(h + sym_b) : (void*)h_iq, d_iq, samples * sizeof(cf32), hipMemcpyDeviceToHost,
-                          st));
-    HIP_OK(hipStreamSynchronize(st));
-    if (h) std::memcpy(h_iq, h + sym_b, samples * sizeof(cf32));
-    return 0;
-}
-
 }  // extern "C"
+
+#include "lphy_host.h"

@@ -1,0 +1,141 @@
+// lphy_stage_plan.h — where the buffers of one *_host call lie in the
+// context's staging (lphy_host.h): an ordered list of slices, the bytes the
+// call needs, and the spans the pinned mirror moves in one copy each way.
+// Plain host arithmetic, no HIP: the CPU tests compile it alone
+// (tests/cpp/stage_plan_check.cpp).
+#pragma once
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+
+#include "lphy_ragged_layout.h"
+
+namespace lphy {
+
+// every slice starts on this alignment and occupies at least one unit of it,
+// so the slices of a call are distinct and non-null even when empty
+constexpr size_t align_up(size_t x) { return (x + 255) & ~size_t(255); }
+
+enum StageRole : unsigned {
+    kStageIn = 1,       // host -> device before the kernels
+    kStageOut = 2,      // device -> host after them
+    kStageInOut = 3,
+    kStageZero = 4,     // device memory zeroed before the kernels
+    kStageZeroOut = 6,
+    kStageScratch = 8,  // lent to the kernels, never copied; after every other slice
+};
+
+struct StageSlice {
+    size_t off = 0, size = 0;
+    unsigned role = 0;
+};
+
+struct StageSpan {  // [begin, end); begin == end: nothing to move
+    size_t begin = 0, end = 0;
+    void cover(size_t b, size_t e) {
+        if (begin == end) begin = b;
+        end = e;
+    }
+};
+
+struct StagePlan {
+    static constexpr int kMaxSlices = 5;
+    StageSlice s[kMaxSlices];
+    int n = 0;
+    size_t end = 0;         // bytes of staging the call needs
+    size_t copied_end = 0;  // end of the last slice that is not scratch
+    StageSpan up, down;     // the non-empty slices uploaded or zeroed / downloaded
+
+    StagePlan& add(size_t size, unsigned role) {
+        s[n++] = StageSlice{end, size, role};
+        const size_t off = end;
+        end += align_up(std::max<size_t>(1, size));
+        if (role == kStageScratch) return *this;
+        copied_end = end;
+        if (size && (role & (kStageIn | kStageZero))) up.cover(off, end);
+        if (size && (role & kStageOut)) down.cover(off, end);
+        return *this;
+    }
+};
+
+constexpr size_t kIqBytes = 2 * sizeof(float);  // one complex sample
+constexpr size_t kMetaBytes = sizeof(lphy_frame_meta);
+
+// The plans of the eight *_host entry points, slices in the order named.
+
+// iq | syms | bytes | meta | spec (the SF 11-12 speculation records); `per`:
+// lphy_hip_syms_per_frame
+inline StagePlan demod_plan(size_t frames, size_t frame_samples, size_t per) {
+    return StagePlan()
+        .add(frames * frame_samples * kIqBytes, kStageIn)
+        .add(frames * per * sizeof(uint16_t), kStageOut)
+        .add(frames * (per / 2), kStageOut)
+        .add(frames * kMetaBytes, kStageZeroOut)
+        .add(frames * 16, kStageScratch);
+}
+
+// iq | desc | syms | bytes | meta; the caller's output slots go in as well
+// (slots no frame owns come back as they went)
+inline StagePlan ragged_plan(size_t iq_samples, size_t frames, size_t out_syms) {
+    return StagePlan()
+        .add(iq_samples * kIqBytes, kStageIn)
+        .add((frames + 1) * sizeof(lphy_ragged_desc), kStageIn)
+        .add(out_syms * sizeof(uint16_t), kStageInOut)
+        .add((out_syms + 1) / 2, kStageInOut)
+        .add(frames * kMetaBytes, kStageZeroOut);
+}
+
+// iq (the samples the windows span) | records
+inline StagePlan detect_plan(size_t span, size_t windows) {
+    return StagePlan().add(span * kIqBytes, kStageIn).add(windows * sizeof(lphy_detect_rec), kStageOut);
+}
+
+// syms | bytes | meta
+inline StagePlan decode_plan(size_t count) {
+    return StagePlan().add(count * sizeof(uint16_t), kStageIn).add(count / 2, kStageOut).add(kMetaBytes, kStageZeroOut);
+}
+
+// iq | meta
+inline StagePlan estimate_plan(size_t count) {
+    return StagePlan().add(count * kIqBytes, kStageIn).add(kMetaBytes, kStageInOut);
+}
+
+// iq | the time shift's buffer
+inline StagePlan compensate_plan(size_t count) {
+    return StagePlan().add(count * kIqBytes, kStageInOut).add(count * kIqBytes, kStageScratch);
+}
+
+// iq | meta
+inline StagePlan compensate_batch_plan(size_t frames, size_t frame_samples) {
+    return StagePlan().add(frames * frame_samples * kIqBytes, kStageInOut).add(frames * kMetaBytes, kStageIn);
+}
+
+// syms | iq | the modulator's scratch (mod_scratch_bytes for one frame of nsyms); step = N * osr
+inline StagePlan modulate_plan(size_t step, size_t nsyms, size_t scratch) {
+    return StagePlan()
+        .add(nsyms * sizeof(uint16_t), kStageIn)
+        .add((nsyms + 2) * step * kIqBytes, kStageOut)
+        .add(scratch, kStageScratch);
+}
+
+// Staging every *_host entry point needs for calls of up to `frames` frames
+// of `frame_samples` samples, or one buffer of frames * frame_samples: the
+// largest of the eight plans at that shape.  Demodulation in modes 1/2, which
+// give no fewer symbols than mode 0; ragged frames of frame_samples each; one
+// detector window per N samples of the buffer; all the frames' symbols in one
+// decode; one frame's symbols in one modulate (mod_scratch: its
+// mod_scratch_bytes).  A call past that grows the staging.
+inline size_t host_stage_bytes(size_t N, size_t osr, size_t frames, size_t frame_samples, size_t mod_scratch) {
+    const size_t step = N * osr, n = frames * frame_samples, total = frame_samples / step;
+    const size_t per = ragged_out_syms(total, LPHY_MODE_LORA_DEMODULATE);
+    return std::max({demod_plan(frames, frame_samples, per).end,
+                     ragged_plan(n, frames, frames * ((per + 1) & ~size_t(1))).end,
+                     detect_plan(n, n / N).end,
+                     decode_plan(frames * (total + 2)).end,
+                     estimate_plan(n).end,
+                     compensate_plan(n).end,
+                     compensate_batch_plan(frames, frame_samples).end,
+                     modulate_plan(step, total, mod_scratch).end});
+}
+
+}  // namespace lphy

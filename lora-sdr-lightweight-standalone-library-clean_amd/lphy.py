@@ -547,6 +547,13 @@ class Demodulator:
         fn.argtypes = [_vp, C.c_int]
         _chk(fn(self.ctx, int(bool(on))), "lphy_hip_test_mod_force_serial")
 
+    def pinned_max(self, nbytes: int) -> None:
+        """Test build only: the largest *_host call that goes through the
+        pinned mirror (0: every call takes the pageable copies)."""
+        fn = self.lib.lphy_hip_test_pinned_max
+        fn.argtypes = [_vp, _sz]
+        _chk(fn(self.ctx, int(nbytes)), "lphy_hip_test_pinned_max")
+
     def recheck_count(self, reset: bool = True) -> int:
         """Symbols the fused kernel re-ran with the exact rotation (device sync)."""
         n = C.c_ulonglong(0)
