@@ -30,7 +30,11 @@
  *   lphy_hip_estimate_batch lora_phy::estimate_offsets src/phy/phy.cpp:81-148
  *   lphy_hip_modulate_batch lora_phy::lora_modulate  src/phy/LoRaMod.cpp:8-43
  *                            (producer; bit-exact, used for synthetic IQ)
- *   lphy_hip_compensate    lora_phy::compensate_offsets src/phy/phy.cpp:150-180
+ *   lphy_hip_modulate_ragged lora_phy::lora_modulate src/phy/LoRaMod.cpp:8-43
+ *                            for frames of different lengths in one call
+ *   lphy_hip_tx_ragged       lora_phy::lora_encode   src/phy/LoRaEncoder.cpp:6-18
+ *                            fused in front of it: bytes in, IQ out
+ *   lphy_hip_compensate   lora_phy::compensate_offsets src/phy/phy.cpp:150-180
  *   lphy_hip_compensate_batch  the same for every frame of a batch, each with its
  *   lphy_hip_compensate_ragged own offsets read on the device from its
  *                          lphy_frame_meta (frames of one length / of different
@@ -124,7 +128,8 @@ int lphy_hip_ctx_share(lphy_hip_ctx** out, const lphy_hip_ctx* base, unsigned os
  * calls allocate nothing: the reference allocates nothing after init
  * (API_SPEC.md:9-14; lora_demod_init's max_samples, LoRaDemod.cpp:11-33).
  * The size covers every *_host form at that shape: frames of frame_samples
- * each, or one buffer of frames * frame_samples samples.
+ * each, or one buffer of frames * frame_samples samples (the ragged receive
+ * and transmit forms: `frames` frames of up to frame_samples each).
  * A larger call later grows the staging once.  Returns 0 or -ENOMEM/-EIO. */
 int lphy_hip_ctx_reserve(lphy_hip_ctx* ctx, size_t frames, size_t frame_samples);
 
@@ -369,10 +374,85 @@ int lphy_hip_compensate_ragged(lphy_hip_ctx* ctx, const float* d_in, float* d_ou
 
 /* lora_modulate (LoRaMod.cpp:8-43) for `frames` frames of `nsyms` symbols
  * each (d_syms + f*nsyms) into d_iq + 2*f*(nsyms+2)*N*osr floats; bit-exact
- * with the reference.  Producer for synthetic input, not on the timed path. */
+ * with the reference.  Producer for synthetic input, not on the timed path
+ * (the transmit path built for throughput is lphy_hip_modulate_ragged /
+ * lphy_hip_tx_ragged, below, which also take frames of one length). */
 int lphy_hip_modulate_batch(lphy_hip_ctx* ctx, const uint16_t* d_syms,
                             size_t frames, size_t nsyms, float* d_iq,
                             float amplitude, uint8_t sync, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Ragged transmit: encode and modulate frames of different lengths in one
+ * call, on the same lphy_ragged_desc table as the receive side.  A table made
+ * by lphy_hip_tx_layout (or lphy_hip_ragged_layout in mode
+ * LPHY_MODE_LORA_DEMODULATE on samples = (2*len + 2) * N * osr) serves both
+ * directions: lphy_hip_tx_ragged turns bytes into IQ, and
+ * lphy_hip_demod_ragged(..., LPHY_MODE_DECHIRP_LORA_DEMODULATE, LPHY_F_DECODE)
+ * on the same table turns that IQ back into bytes at the same offsets.
+ *
+ * Frame f, with step = N * osr and total = samples / step:
+ *   - total < 2: the frame writes nothing.  Otherwise nsyms = total - 2.
+ *   - lphy_hip_modulate_ragged reads nsyms symbols at d_syms + sym_offset.
+ *     lphy_hip_tx_ragged reads nsyms / 2 bytes at d_bytes + sym_offset / 2;
+ *     byte j gives symbols 2j and 2j + 1, encodeHamming84sx of its high, then
+ *     its low nibble (LoRaCodes.hpp:229-242); it modulates 2 * (nsyms / 2)
+ *     data symbols and, when d_syms_out is not NULL, also stores them at
+ *     d_syms_out + sym_offset.
+ *   - The IQ goes to d_iq + 2 * iq_offset floats: sync symbol 0, sync symbol
+ *     1, the data symbols; bit for bit what lora_modulate gives for that frame
+ *     alone with the context's sf, bandwidth and osr.  The phase starts at 0
+ *     in every frame; the amplitude is clamped to [-1, 1] (LoRaMod.cpp:18).
+ *   - The frame's samples past its last modulated symbol, the gaps between
+ *     frames and d_syms_out outside the frames' slots are left untouched.
+ *   - unit_offset is read: the exclusive prefix sum of total in record order,
+ *     the sum in record [frames], as for lphy_hip_demod_ragged.  Frames may
+ *     lie in any address order and must not overlap.
+ *
+ * Returns -EINVAL for a null ctx, then 0 for frames == 0; -EINVAL for a null
+ * d_syms / d_bytes, d_desc or d_iq (the device forms cannot see whether any
+ * data symbol exists, so the source is always required there); -ERANGE for
+ * frames >= 2^31; -ENOTSUP for SF < 7.  Every osr the context accepts is in
+ * scope.
+ *
+ * The device forms are asynchronous on `stream`, allocate nothing on the
+ * device and read no descriptor on the host.  Two launches: one thread per
+ * frame walks the frame's phase recurrence and parks the phase at each symbol
+ * start in that symbol's own first output sample; a persistent grid over the
+ * symbols then writes every sample with 16-byte stores ("Ragged
+ * transmit").  This path is for throughput: many frames per call.  A single
+ * packet stays lphy_hip_modulate_host's case, whose walk is parallel within
+ * the frame.
+ *
+ * The host form goes through the context's stream and staging like
+ * lphy_hip_demod_host, and checks the table before any device call: the
+ * limits and the prefix as lphy_hip_demod_ragged_host, and -EINVAL for a frame
+ * with samples % step != 0, with total < 2 or with an odd nsyms.  h_bytes may
+ * be NULL only when no frame has data symbols; h_syms_out may be NULL.  h_iq
+ * and h_syms_out span the descriptors' extent; what no frame owns keeps the
+ * caller's values (those buffers are uploaded only when the frames leave gaps
+ * in them).
+ * --------------------------------------------------------------------- */
+int lphy_hip_modulate_ragged(lphy_hip_ctx* ctx, const uint16_t* d_syms,
+                             const lphy_ragged_desc* d_desc, size_t frames,
+                             float* d_iq, float amplitude, uint8_t sync,
+                             void* stream);
+int lphy_hip_tx_ragged(lphy_hip_ctx* ctx, const uint8_t* d_bytes,
+                       const lphy_ragged_desc* d_desc, size_t frames,
+                       float* d_iq, uint16_t* d_syms_out /* may be NULL */,
+                       float amplitude, uint8_t sync, void* stream);
+int lphy_hip_tx_ragged_host(lphy_hip_ctx* ctx, const uint8_t* h_bytes,
+                            const lphy_ragged_desc* h_desc, size_t frames,
+                            float* h_iq, uint16_t* h_syms_out, float amplitude,
+                            uint8_t sync);
+
+/* Host-only, no device work: h_desc[frames + 1] for frames of h_len_bytes[f]
+ * payload bytes, packed back to back: lphy_hip_ragged_layout in mode
+ * LPHY_MODE_LORA_DEMODULATE on samples = (2*len + 2) * N * osr, so sym_offset
+ * / 2 is the exclusive prefix of len.  Returns 0, -EINVAL (null pointer),
+ * -ERANGE (a frame of 2^31 samples or more, or the limits of
+ * lphy_hip_ragged_layout) or -ENOMEM. */
+int lphy_hip_tx_layout(const lphy_hip_ctx* ctx, const uint64_t* h_len_bytes,
+                       size_t frames, lphy_ragged_desc* h_desc);
 
 /* Host-buffer convenience used by the C++ shim: uploads, runs
  * lphy_hip_demod_batch, downloads, on the context's own stream and staging

@@ -3,11 +3,13 @@
 // kernels (lphy_route.h) and their launch through the per-SF tables (SfOps:
 // the kernels templated on SF are the lphy_sf.hip objects'), and the
 // SF-independent kernels themselves: the finalisation (k_finalize), the
-// modulator and the compensation (lphy_mod.h), k_mark_recheck.  The host-
+// modulator and the compensation (lphy_mod.h), the ragged transmit path
+// (lphy_tx.h), k_mark_recheck.  The host-
 // buffer forms (*_host) are lphy_host.h, included at the end.
 #include "lphy_args.h"
 #include "lphy_final.h"
 #include "lphy_mod.h"
+#include "lphy_tx.h"
 #include "lphy_route.h"
 #include "lphy_stage_plan.h"
 #include "lphy_testing.h"
@@ -933,6 +935,82 @@ int lphy_hip_modulate_batch(lphy_hip_ctx* c, const uint16_t* d_syms, size_t fram
     HIP_OK(hipSetDevice(c->device));
     return modulate_impl(c, d_syms, frames, nsyms, d_iq, amplitude, sync, (hipStream_t)stream,
                          nullptr);
+}
+
+// ---- ragged transmit (lphy_tx.h) -------------------------------------------
+int lphy_hip_tx_layout(const lphy_hip_ctx* c, const uint64_t* h_len_bytes, size_t frames,
+                       lphy_ragged_desc* h_desc) {
+    if (!c) return -EINVAL;
+    return tx_layout((uint64_t)c->N * c->osr, h_len_bytes, frames, h_desc);
+}
+
+namespace {
+// The argument checks the three forms share, in the header's order (`src`: the
+// symbols or the bytes): 0 to go on, 1 when there is nothing to do, or the error.
+int tx_check(const lphy_hip_ctx* c, const void* src, const void* desc, size_t frames, const void* iq) {
+    if (!c) return -EINVAL;
+    if (frames == 0) return 1;
+    if (!src || !desc || !iq) return -EINVAL;
+    if (frames > 0x7fffffffULL) return -ERANGE;
+    if (c->sf < 7) return -ENOTSUP;
+    return 0;
+}
+
+extern "C++" {
+// k_tx_samples<SRC>'s persistent grid: every workgroup the device holds at
+// once, found once per device (the device form does not know the call's units).
+template <class SRC>
+unsigned tx_resident_grid(int device) {
+    static unsigned grid[64];
+    static std::once_flag once[64];
+    const int d = device >= 0 && device < 64 ? device : 0;
+    std::call_once(once[d], [d, device] {
+        int per = 0, cus = 0;
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_tx_samples<SRC>, kTile, 0);
+        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+        grid[d] = (unsigned)((cus > 0 ? cus : 256) * (per > 0 ? per : 1));
+    });
+    return grid[d];
+}
+
+// The two launches.  units_hint: the call's whole symbols when the caller's
+// table is on the host (the sample pass's grid then stops at its tiles).
+template <class SRC>
+int tx_launch(const lphy_hip_ctx* c, SRC src, const lphy_ragged_desc* d_desc, size_t frames, float* d_iq,
+              uint16_t* d_syms_out, float amplitude, uint8_t sync, hipStream_t st, unsigned long long units_hint) {
+    TxArgs A{};
+    A.desc = d_desc;
+    A.iq = reinterpret_cast<cf32*>(d_iq);
+    A.syms_out = d_syms_out;
+    A.frames = (unsigned)frames;
+    A.N = (int)c->N;
+    A.osr = (int)c->osr;
+    A.shift = (int)c->sf - 4;
+    A.bws = (float)c->bw_hz / 125000.0f;
+    A.ampl = std::max(-1.0f, std::min(1.0f, amplitude));  // LoRaMod.cpp:18
+    A.sync = sync;
+    unsigned grid = tx_resident_grid<SRC>(c->device);
+    if (units_hint) grid = (unsigned)std::min<unsigned long long>(grid, (units_hint + kTile - 1) / kTile);
+    hipLaunchKernelGGL(k_tx_walk<SRC>, dim3((unsigned)((frames + 63) / 64)), dim3(64), 0, st, A, src);
+    hipLaunchKernelGGL(k_tx_samples<SRC>, dim3(grid), dim3(kTile), 0, st, A, src);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+}  // extern "C++"
+}  // namespace
+
+int lphy_hip_modulate_ragged(lphy_hip_ctx* c, const uint16_t* d_syms, const lphy_ragged_desc* d_desc, size_t frames,
+                             float* d_iq, float amplitude, uint8_t sync, void* stream) {
+    if (int rc = tx_check(c, d_syms, d_desc, frames, d_iq)) return rc > 0 ? 0 : rc;
+    HIP_OK(hipSetDevice(c->device));
+    return tx_launch(c, TxSymbols{d_syms}, d_desc, frames, d_iq, nullptr, amplitude, sync, (hipStream_t)stream, 0);
+}
+
+int lphy_hip_tx_ragged(lphy_hip_ctx* c, const uint8_t* d_bytes, const lphy_ragged_desc* d_desc, size_t frames,
+                       float* d_iq, uint16_t* d_syms_out, float amplitude, uint8_t sync, void* stream) {
+    if (int rc = tx_check(c, d_bytes, d_desc, frames, d_iq)) return rc > 0 ? 0 : rc;
+    HIP_OK(hipSetDevice(c->device));
+    return tx_launch(c, TxBytes{d_bytes}, d_desc, frames, d_iq, d_syms_out, amplitude, sync, (hipStream_t)stream, 0);
 }
 
 int lphy_hip_sync(void* stream) {

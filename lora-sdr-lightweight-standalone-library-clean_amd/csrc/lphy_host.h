@@ -28,7 +28,7 @@ int ensure_host_stage(lphy_hip_ctx* c, size_t bytes) {
 //
 // kMirror: demod, decode and modulate (the per-packet calls of the lora_phy::
 // API) go through the pinned mirror when their copied slices fit
-// it, one DMA copy each way; the other five copy slice by slice from and to
+// it, one DMA copy each way; the other six copy slice by slice from and to
 // the caller's memory.  Which call does which is a measured choice, not an
 // accident of this code.
 enum HostCopy { kPageable, kMirror };
@@ -225,6 +225,29 @@ int lphy_hip_modulate_host(lphy_hip_ctx* c, const uint16_t* h_syms, size_t nsyms
         return rc;
     return hc.finish(modulate_impl(c, hc.dev<uint16_t>(0), 1, nsyms, hc.dev<float>(1), amplitude, sync, hc.stream(),
                                    hc.dev<void>(2)));
+}
+
+// The ragged transmit call on host buffers: bytes and descriptors in (and the
+// caller's IQ / symbols where the frames leave gaps in them), the two
+// launches, IQ and symbols out.  The table is checked before any device call.
+int lphy_hip_tx_ragged_host(lphy_hip_ctx* c, const uint8_t* h_bytes, const lphy_ragged_desc* h_desc, size_t frames,
+                            float* h_iq, uint16_t* h_syms_out, float amplitude, uint8_t sync) {
+    if (!c) return -EINVAL;
+    if (frames == 0) return 0;
+    if (!h_desc || !h_iq) return -EINVAL;
+    if (frames > 0x7fffffffULL) return -ERANGE;
+    if (c->sf < 7) return -ENOTSUP;
+    TxExtent x;
+    if (int rc = tx_extent((uint64_t)c->N * c->osr, h_desc, frames, &x)) return rc;
+    if (x.in_bytes && !h_bytes) return -EINVAL;
+    const size_t out_syms = h_syms_out ? (size_t)x.out_syms : 0;
+    HostCall hc(c, kPageable);
+    if (int rc = hc.begin(tx_plan(x.in_bytes, frames, x.iq_samples, out_syms, x.iq_gaps, x.sym_gaps),
+                          {h_bytes, h_desc, h_iq, h_syms_out}))
+        return rc;
+    return hc.finish(tx_launch(c, TxBytes{hc.dev<uint8_t>(0)}, hc.dev<lphy_ragged_desc>(1), frames, hc.dev<float>(2),
+                               h_syms_out ? hc.dev<uint16_t>(3) : nullptr, amplitude, sync, hc.stream(),
+                               h_desc[frames].unit_offset));
 }
 
 }  // extern "C"

@@ -90,7 +90,8 @@ struct ChirpWalk {
     }
 };
 
-__device__ __forceinline__ ChirpWalk chirp_walk(const ModArgs& A) {
+template <class ARGS>  // (ModArgs, TxArgs: N, osr, bws)
+__device__ __forceinline__ ChirpWalk chirp_walk(const ARGS& A) {
     ChirpWalk w;
     w.fmin = -kPi * A.bws / (float)A.osr;
     w.fmax = kPi * A.bws / (float)A.osr;

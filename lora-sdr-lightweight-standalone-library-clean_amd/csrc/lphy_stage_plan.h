@@ -61,7 +61,7 @@ struct StagePlan {
 constexpr size_t kIqBytes = 2 * sizeof(float);  // one complex sample
 constexpr size_t kMetaBytes = sizeof(lphy_frame_meta);
 
-// The plans of the eight *_host entry points, slices in the order named.
+// The plans of the nine *_host entry points, slices in the order named.
 
 // iq | syms | bytes | meta | spec (the SF 11-12 speculation records); `per`:
 // lphy_hip_syms_per_frame
@@ -118,12 +118,25 @@ inline StagePlan modulate_plan(size_t step, size_t nsyms, size_t scratch) {
         .add(scratch, kStageScratch);
 }
 
+// bytes | desc | iq | syms (lphy_hip_tx_ragged_host).  The IQ and the symbols
+// are outputs; where the frames leave gaps in them the caller's values go in
+// first, so that the gaps come back as they went.  out_syms = 0: no h_syms_out.
+inline StagePlan tx_plan(size_t in_bytes, size_t frames, size_t iq_samples, size_t out_syms, bool iq_gaps,
+                         bool sym_gaps) {
+    return StagePlan()
+        .add(in_bytes, kStageIn)
+        .add((frames + 1) * sizeof(lphy_ragged_desc), kStageIn)
+        .add(iq_samples * kIqBytes, iq_gaps ? kStageInOut : kStageOut)
+        .add(out_syms * sizeof(uint16_t), sym_gaps ? kStageInOut : kStageOut);
+}
+
 // Staging every *_host entry point needs for calls of up to `frames` frames
 // of `frame_samples` samples, or one buffer of frames * frame_samples: the
-// largest of the eight plans at that shape.  Demodulation in modes 1/2, which
+// largest of the nine plans at that shape.  Demodulation in modes 1/2, which
 // give no fewer symbols than mode 0; ragged frames of frame_samples each; one
 // detector window per N samples of the buffer; all the frames' symbols in one
-// decode; one frame's symbols in one modulate (mod_scratch: its
+// decode; ragged transmit frames of frame_samples each, gaps or not (the
+// ragged plan's slices less the records, so it never sets the size); one frame's symbols in one modulate (mod_scratch: its
 // mod_scratch_bytes).  A call past that grows the staging.
 inline size_t host_stage_bytes(size_t N, size_t osr, size_t frames, size_t frame_samples, size_t mod_scratch) {
     const size_t step = N * osr, n = frames * frame_samples, total = frame_samples / step;
@@ -135,7 +148,8 @@ inline size_t host_stage_bytes(size_t N, size_t osr, size_t frames, size_t frame
                      estimate_plan(n).end,
                      compensate_plan(n).end,
                      compensate_batch_plan(frames, frame_samples).end,
-                     modulate_plan(step, total, mod_scratch).end});
+                     modulate_plan(step, total, mod_scratch).end,
+                     tx_plan(frames * (per / 2), frames, n, frames * ((per + 1) & ~size_t(1)), true, true).end});
 }
 
 }  // namespace lphy

@@ -109,6 +109,7 @@ EXPORTS = (
     "lphy_hip_ragged_layout", "lphy_hip_demod_ragged", "lphy_hip_demod_ragged_host",
     "lphy_hip_detect_batch", "lphy_hip_detect_host", "lphy_hip_detect_serial_count",
     "lphy_hip_compensate_batch", "lphy_hip_compensate_ragged", "lphy_hip_compensate_batch_host",
+    "lphy_hip_modulate_ragged", "lphy_hip_tx_ragged", "lphy_hip_tx_ragged_host", "lphy_hip_tx_layout",
 )
 
 WHITEN_SX1232, WHITEN_SX1272, WHITEN_SX1272_LFSR = 0, 1, 2
@@ -175,6 +176,10 @@ def load(path: Path | None = None) -> C.CDLL:
     L.lphy_hip_compensate_ragged.argtypes = [_vp, _vp, _vp, _vp, _sz, _vp, _vp]
     L.lphy_hip_compensate_batch_host.argtypes = [_vp, _vp, _sz, _sz, _vp]
     L.lphy_hip_modulate_batch.argtypes = [_vp, _vp, _sz, _sz, _vp, C.c_float, C.c_uint8, _vp]
+    L.lphy_hip_modulate_ragged.argtypes = [_vp, _vp, _vp, _sz, _vp, C.c_float, C.c_uint8, _vp]
+    L.lphy_hip_tx_ragged.argtypes = [_vp, _vp, _vp, _sz, _vp, _vp, C.c_float, C.c_uint8, _vp]
+    L.lphy_hip_tx_ragged_host.argtypes = [_vp, _vp, _vp, _sz, _vp, _vp, C.c_float, C.c_uint8]
+    L.lphy_hip_tx_layout.argtypes = [_vp, _vp, _sz, _vp]
     L.lphy_hip_demod_host.argtypes = [_vp, _vp, _sz, _sz, _vp, _vp, _vp, C.c_int, C.c_uint]
     L.lphy_hip_decode_host.argtypes = [_vp, _vp, _sz, _vp, _vp]
     L.lphy_hip_estimate_host.argtypes = [_vp, _vp, _sz, _vp]
@@ -380,6 +385,83 @@ class Demodulator:
         _chk(self.lib.lphy_hip_modulate_batch(self.ctx, p_syms, frames, nsyms, p_iq,
                                               amplitude, sync, stream),
              "lphy_hip_modulate_batch")
+
+    # --- ragged transmit: frames of different lengths in one call --------
+    def tx_layout(self, len_bytes) -> np.ndarray:
+        """Descriptors (RAGGED_DESC_DTYPE, len(len_bytes) + 1 records) of frames
+        carrying `len_bytes` payload bytes each, (2 len + 2) symbols packed
+        back to back (lphy_hip_tx_layout): frame f's bytes start at
+        desc["sym_offset"][f] // 2.  The same table demodulates the IQ."""
+        n = np.ascontiguousarray(len_bytes, np.uint64).reshape(-1)
+        desc = np.zeros(n.size + 1, RAGGED_DESC_DTYPE)
+        _chk(self.lib.lphy_hip_tx_layout(self.ctx, n.ctypes.data if n.size else None, n.size, desc.ctypes.data),
+             "lphy_hip_tx_layout")
+        return desc
+
+    def modulate_ragged(self, syms, desc, frames, iq, amplitude=1.0, sync=0x12, stream=None,
+                        iq_samples=None, out_syms=None):
+        """lphy_hip_modulate_ragged on device tensors: frame f's symbols at
+        syms[desc[f]["sym_offset"]:], its IQ at iq[2 * desc[f]["iq_offset"]:]
+        floats.  `desc`: device tensor of frames + 1 RAGGED_DESC_DTYPE records.
+        iq_samples / out_syms: the extents the descriptors span (checked
+        against the tensors).  Asynchronous."""
+        dv = self.device
+        p_syms = _dev_buf(syms, "syms", dv, (out_syms or 0) * 2, 2)
+        p_desc = _dev_buf(desc, "desc", dv, (frames + 1) * 32, None)
+        p_iq = _dev_buf(iq, "iq", dv, (iq_samples or 0) * 8, None)
+        _chk(self.lib.lphy_hip_modulate_ragged(self.ctx, p_syms, p_desc, frames, p_iq, amplitude, sync, stream),
+             "lphy_hip_modulate_ragged")
+
+    def tx_ragged(self, data, desc, frames, iq, syms_out=None, amplitude=1.0, sync=0x12, stream=None,
+                  iq_samples=None, out_syms=None):
+        """lphy_hip_tx_ragged on device tensors: lora_encode + lora_modulate of
+        frame f's bytes at data[desc[f]["sym_offset"] // 2:].  syms_out
+        (optional) receives the encoded symbols at sym_offset.  Asynchronous."""
+        dv = self.device
+        p_data = _dev_buf(data, "data", dv, ((out_syms or 0) + 1) // 2, 1)
+        p_desc = _dev_buf(desc, "desc", dv, (frames + 1) * 32, None)
+        p_iq = _dev_buf(iq, "iq", dv, (iq_samples or 0) * 8, None)
+        p_out = _dev_buf(syms_out, "syms_out", dv, (out_syms or 0) * 2, 2) if syms_out is not None else None
+        _chk(self.lib.lphy_hip_tx_ragged(self.ctx, p_data, p_desc, frames, p_iq, p_out, amplitude, sync, stream),
+             "lphy_hip_tx_ragged")
+
+    def tx_ragged_host(self, payloads_or_data, desc=None, amplitude=1.0, sync=0x12, iq=None, syms_out=None,
+                       want_syms=True):
+        """Encode and modulate frames of different lengths in one call.  Either a
+        list of payloads (bytes / uint8 arrays; the table comes from tx_layout)
+        or a flat uint8 array with a RAGGED_DESC_DTYPE table of frames + 1
+        records.  iq / syms_out: the caller's buffers over the descriptors'
+        extent (what no frame owns keeps its values); made here when None.
+        Returns (iq complex64, symbols uint16 or None, desc)."""
+        if desc is None:
+            pl = [np.frombuffer(bytes(p), np.uint8) for p in payloads_or_data]
+            desc = self.tx_layout([p.size for p in pl])
+            data = np.concatenate(pl) if pl else np.zeros(0, np.uint8)
+        else:
+            desc = np.ascontiguousarray(desc, RAGGED_DESC_DTYPE)
+            data = np.ascontiguousarray(payloads_or_data, np.uint8).reshape(-1)
+        frames = desc.size - 1
+        n_iq, n_out = self._ragged_extent(desc, MODE_LORA_DEMODULATE)
+        d = desc[:-1]
+        total = np.maximum(d["samples"] // np.uint64(self.N * self.osr), np.uint64(2))
+        need = int((d["sym_offset"] // np.uint64(2) + (total - np.uint64(2)) // np.uint64(2)).max()) if frames else 0
+        if data.size < need:
+            raise ValueError(f"data: {data.size} bytes, the descriptors read {need}")
+        if iq is None:
+            iq = np.zeros(max(n_iq, 1), np.complex64)
+        if iq.dtype != np.complex64 or not iq.flags.c_contiguous or iq.size < n_iq:
+            raise ValueError(f"iq: contiguous complex64 of at least {n_iq} samples expected")
+        if syms_out is None and want_syms:
+            syms_out = np.zeros(max(n_out, 1), np.uint16)
+        if syms_out is not None and (syms_out.dtype != np.uint16 or not syms_out.flags.c_contiguous
+                                     or syms_out.size < n_out):
+            raise ValueError(f"syms_out: contiguous uint16 of at least {n_out} symbols expected")
+        pad = np.zeros(1, np.uint8)
+        _chk(self.lib.lphy_hip_tx_ragged_host(self.ctx, (data if data.size else pad).ctypes.data, desc.ctypes.data,
+                                              frames, iq.ctypes.data,
+                                              syms_out.ctypes.data if syms_out is not None else None,
+                                              amplitude, sync), "lphy_hip_tx_ragged_host")
+        return iq, syms_out, desc
 
     def decode_batch(self, syms, frames, syms_per_frame, payload, meta, stream=None):
         dv = self.device
