@@ -4,7 +4,10 @@
 // identical FFT (lphy_fft.h) -> |X|^2 argmax (LoRaDemod.cpp:142-176 /
 // phy.cpp:204-238).  Also the symbol machinery the other demodulator kernels
 // share (lphy_frames.h, lphy_post.h, lphy_wave.h): SymCtx, rotate_sample,
-// the staging, UnitResult, EstFold, the certificate.
+// the staging, UnitResult, EstFold, the certificate; and the exact passes of
+// the paths that reproduce the reference's arithmetic plainly (k_maxabs,
+// k_estimate, lphy_post.h, lphy_ragged.h): workgroup_max, estimate_unit,
+// exact_symbol, settle_verdict, and the ragged tables' unit_frame.
 #pragma once
 #include "lphy_args.h"
 #include "libm_exact.h"
@@ -42,6 +45,23 @@ __device__ __forceinline__ void maxabs_acc(float& mx, cf32 x) {
     const float r = fabsf(x.x), im = fabsf(x.y);
     const float m = (r < im) ? im : r;
     if (m > mx) mx = m;
+}
+
+// The workgroup's maximum of every lane's mx (order-free), through
+// wmax[kTile / 64].  One barrier: the whole workgroup calls it, and another
+// barrier stands before wmax is written again.
+__device__ __forceinline__ float workgroup_max(float mx, float* wmax) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const float o = __shfl_xor(mx, off, 64);
+        mx = o > mx ? o : mx;
+    }
+    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    mx = wmax[0];
+#pragma unroll
+    for (int w = 1; w < kTile / 64; ++w) mx = wmax[w] > mx ? wmax[w] : mx;
+    return mx;
 }
 
 // Normalisation decision of LoRaDemod.cpp:60-78 from the frame's max-abs.
@@ -112,22 +132,14 @@ __global__ __launch_bounds__(kTile) void k_maxabs(DemodArgs A) {
     } else {
         for (unsigned long long i = tid; i < count; i += kTile) acc(fr[i], i);
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const float o = __shfl_xor(mx, off, 64);
-        mx = o > mx ? o : mx;
-    }
+    // a wave that met a non-finite sample enters NaN, which its wmax entry
+    // keeps (a NaN loses every comparison of the maximum)
     if (__ballot(bad)) mx = __builtin_nanf("");
-    if ((tid & 63) == 0) wmax[tid >> 6] = mx;
-    __syncthreads();
+    mx = workgroup_max(mx, wmax);
     if (tid == 0) {
-        mx = wmax[0];
-        bool nf = !(mx == mx);
+        bool nf = false;
 #pragma unroll
-        for (int w = 1; w < kTile / 64; ++w) {
-            nf |= !(wmax[w] == wmax[w]);
-            mx = wmax[w] > mx ? wmax[w] : mx;
-        }
+        for (int w = 0; w < kTile / 64; ++w) nf |= !(wmax[w] == wmax[w]);
         A.meta[f] = norm_meta_hot(nf ? __builtin_nanf("") : mx, A.total_syms >= 2, A.no_scratch);
         if (A.spec_big) A.spec_big[f] = make_uint4(__float_as_uint(nf ? 0.0f : mx), 0u, 0x7f7fffffu, nf ? 1u : 0u);
     }
@@ -147,6 +159,9 @@ struct UnitResult {
     float phase;
     int nan;     // a NaN bin (k_frames: the frame goes to the exact re-run)
 };
+// a unit without a symbol (the tail of a tile); an unset best bin is (0, 0),
+// whose atan2 is 0
+constexpr UnitResult kNoUnit{0, 0, 0.0f, 0.0f, 0};
 
 // Detector outputs of one estimate unit from its FFT bins, which the team
 // has written back to its LDS slot (LoRaDetector.hpp:60-71).
@@ -180,6 +195,42 @@ __device__ __forceinline__ float detector_power(float max_value, float power_sca
     const float fund = sqrtf(max_value);
     const float db = 20.0f * lphy_libm::log10f_exact(fund);
     return db - power_scale;
+}
+
+// One estimate unit per team, in the reference's arithmetic
+// (LoRaDemod.cpp:86-92): osr phase t of estimate symbol s of the frame at fr,
+// whose element i is sample (s N + i) osr + t (the reference's sym[t + i osr]),
+// staged through est_sample in natural order; the exact FFT;
+// the bins written back to the team's slot for the interpolation and the
+// phase; the argmax, which it returns: the team's lane 0 then takes the
+// detector outputs from the slot (unit_result; kNoUnit when not live; the
+// osr > 1 power from the winner's |X|^2).  Holds the two barriers between
+// staging and the result, so the whole workgroup calls it; the barriers before
+// (the slot's previous readers) and after (the result's readers) are the
+// caller's.  (The same pass stands written out in exact_frame and
+// settle_frames, lphy_post.h, and in k_rg_prologue, lphy_ragged.h, where the
+// helper cost registers: change those with it.)
+template <int SF>
+__device__ __forceinline__ ArgMax estimate_unit(const DemodArgs& A, const cf32* fr, int s, int t, int osr,
+                                                const lphy_frame_meta& m, bool live, cf32* lds,
+                                                int slot, int lam, const cf32* tw, ArgMax* red) {
+    using G = Geo<SF>;
+    const Stage<SF> st(slot, lam);
+#pragma unroll
+    for (int e = 0; e < G::E; ++e) {
+        const int i = lam + e * G::LPS;
+        cf32 x = czero();
+        if (live) x = est_sample(A, fr, ((unsigned long long)s * G::N + (unsigned)i) * osr + t, i, G::N, m);
+        st.put(lds, e, x);
+    }
+    __syncthreads();
+    cf32 v[16];
+    fft_tile<SF, false, true>(v, lds, slot, lam, tw);
+#pragma unroll
+    for (int e = 0; e < G::E; ++e) lds[G::addr(slot, bin_of<SF>(e, lam))] = v[e];
+    const ArgMax best = symbol_argmax<SF>(local_argmax<SF>(v, lam), red);
+    __syncthreads();
+    return best;
 }
 
 // Running fold of the per-symbol estimates in symbol order
@@ -246,7 +297,6 @@ __global__ __launch_bounds__(kTile) void k_estimate(DemodArgs A) {
     const bool packed = U <= T;
     const int FPT = packed ? T / U : 1;
     const unsigned long long fbase = (unsigned long long)blockIdx.x * FPT;
-    const unsigned long long step = (unsigned long long)N * A.osr;
     for (int i = tid; i < N; i += kTile) twl[i] = A.tw[i];
 
     // fold state of frame (fbase + tid), held by thread tid < FPT
@@ -279,25 +329,10 @@ __global__ __launch_bounds__(kTile) void k_estimate(DemodArgs A) {
         const int s = live ? u / A.osr : 0, t = live ? u % A.osr : 0;
         const cf32* fr = A.iq + f * A.frame_samples;
         __syncthreads();  // previous chunk's readers are done with lds / units
-        // stage natural-order samples sym[t + i*osr] (LoRaDemod.cpp:86-92)
-        const Stage<SF> st(slot, lam);
-#pragma unroll
-        for (int e = 0; e < G::E; ++e) {
-            const int i = lam + e * G::LPS;
-            cf32 x = czero();
-            if (live) x = est_sample(A, fr, (unsigned long long)s * step + t + (unsigned long long)i * A.osr, i, N, m);
-            st.put(lds, e, x);
-        }
-        __syncthreads();
-        cf32 v[16];
-        fft_tile<SF, false, true>(v, lds, slot, lam, twl);
-        // keep the bins for the interpolation and the phase
-#pragma unroll
-        for (int e = 0; e < G::E; ++e) lds[G::addr(slot, bin_of<SF>(e, lam))] = v[e];
-        ArgMax best = symbol_argmax<SF>(local_argmax<SF>(v, lam), red);
-        __syncthreads();
+        // the samples sym[t + i*osr] of symbol s
+        const ArgMax best = estimate_unit<SF>(A, fr, s, t, A.osr, m, live, lds, slot, lam, twl, red);
         if (lam == 0) {
-            units[slot] = live ? unit_result<SF>(lds, slot, best) : UnitResult{0, 0, 0.0f, 0.0f};
+            units[slot] = live ? unit_result<SF>(lds, slot, best) : kNoUnit;
             if (A.osr > 1)
                 upow[slot] = live ? detector_power(best.v > 0.0f ? best.v : 0.0f, A.power_scale) : 0.0f;
         }
@@ -306,7 +341,6 @@ __global__ __launch_bounds__(kTile) void k_estimate(DemodArgs A) {
             const int first = packed ? tid * U : 0;
             const int nu = packed ? U : ((U - c * T) < T ? (U - c * T) : T);
             const bool tie_low = A.mode != LPHY_MODE_DEMODULATE;
-            // an unset best bin is (0, 0), whose atan2 is 0
             for (int k = 0; k < nu; ++k)
                 fold.unit(units[first + k], A.osr > 1 ? upow[first + k] : 0.0f, A.osr, tie_low);
         }
@@ -425,6 +459,26 @@ __device__ __forceinline__ void restage_symbol(cf32* lds, const Stage<SF>& stg, 
         const float ph = c.start + c.rate * (float)i;
         stg.put(lds, e, rotate_sample<SF, MODE, AG>(raw[e], i, c, down, win, lphy_libm::sincosf_needs_large(ph)));
     }
+}
+
+// The team's symbol c of the frame at fr in the reference's arithmetic
+// (k_post's re-runs): restage_symbol with its Annex G products and the
+// call's window, the exact FFT, the argmax.  Holds the barrier between the
+// two, so the whole workgroup calls it; the barrier after the caller's store
+// (before the slot is staged again) is the caller's.
+template <int SF, int MODE>
+__device__ __forceinline__ ArgMax exact_symbol(const DemodArgs& A, const cf32* fr, const SymCtx& c,
+                                               cf32* lds, int slot, int lam, ArgMax* red) {
+    if (A.win)
+        restage_symbol<SF, MODE | kWinBit, true>(lds, Stage<SF>(slot, lam), fr + c.base, c, lam,
+                                                 A.down, A.win, (unsigned)A.osr);
+    else
+        restage_symbol<SF, MODE, true>(lds, Stage<SF>(slot, lam), fr + c.base, c, lam,
+                                       A.down, nullptr, (unsigned)A.osr);
+    __syncthreads();
+    cf32 v[16];
+    fft_tile<SF, false, true>(v, lds, slot, lam, A.tw);
+    return symbol_argmax<SF>(local_argmax<SF>(v, lam), red);
 }
 
 // Stage the team's symbol (rotated, natural order) into its LDS slot.
@@ -557,6 +611,57 @@ __device__ __forceinline__ bool fast_certified(const ArgMax2& b, const SymCtx& c
     const float A = (float)N * 1.41421366f * amax * 1.0001f;
     const float B = cert_bound<SF>(c.rate, c.start, amax, extra);
     return cert_gap(b) > 4.0f * B && A < 1e18f && amax >= 1e-20f && b.v >= 1e-30f;
+}
+
+// Verdict on a frame whose symbols were certified under a speculative
+// normalisation (record sm) that its later samples overturned (settle_frames,
+// k_spec_settle).  e holds the exact normalisation, u0 / u1 the two estimate
+// units transformed again with it; they are folded into e's exact offsets.
+// The symbols stand when the time shift is unchanged and every certified
+// symbol's lead still covers the larger sample bound and the rate difference:
+// a rate error d moves every bin by at most |d| N sum|y_i| <= |d| N A (the
+// phase error of sample i is |d| i), charged twice on both sides of the
+// comparison as fast_certified charges its B.  amax: the frame's max-abs under
+// the speculative scale; lead: the symbols' least certificate ratio; open:
+// some symbols still wait for recheck_frames.  Returns the record to store,
+// status kStatusFixup when the frame must be re-run whole.
+template <int SF>
+__device__ __forceinline__ lphy_frame_meta settle_verdict(const lphy_frame_meta& sm, lphy_frame_meta e,
+                                                          const UnitResult& u0, const UnitResult& u1,
+                                                          float amax, float lead, bool open) {
+    constexpr int N = 1 << SF;
+    EstFold fold;
+    if (u0.valid) fold.add(u0.idx, u0.findex, 0, u0.phase);
+    else fold.add(0, 0.0f, 0, 0.0f);
+    if (u1.valid) fold.add(u1.idx, u1.findex, 0, u1.phase);
+    else fold.add(0, 0.0f, 0, 0.0f);
+    fold.finish(e, 2, N, 1);
+    // amplitude bound of the speculatively scaled samples, and the smallest
+    // bound of any symbol (|start| grows with the symbol)
+    const float a = fmaxf(1.0f, amax) * 1.0001f;
+    const float b1 = cert_bound<SF>(sm.rate, sm.rate * (float)sm.t_off, 1.0f);
+    const float d = fabsf(e.rate - sm.rate) * (1.0f + 4.0f * kU);
+    const float A1 = (float)N * 1.41421366f * 1.0001f;
+    const bool ok = e.t_off == sm.t_off && sm.t_off >= -N && sm.t_off <= N &&
+                    lead > 4.0f * a + 4.0f * d * (float)N * A1 * a / b1;
+    e.sw0 = sm.sw0;
+    e.sw1 = sm.sw1;
+    e.status = !ok ? kStatusFixup : (open ? kStatusRecheck : 0);
+    return e;
+}
+
+// Frame of unit u in a ragged table (lphy_ragged_desc, frames + 1 records):
+// the last record whose unit_offset is <= u, for u below the table's total.
+__device__ __forceinline__ unsigned unit_frame(const lphy_ragged_desc* __restrict__ desc, unsigned nframes,
+                                               unsigned long long u) {
+    // unit_offset[lo] <= u < unit_offset[hi] throughout
+    unsigned lo = 0, hi = nframes;
+    while (hi - lo > 1) {
+        const unsigned mid = lo + ((hi - lo) >> 1);
+        if (desc[mid].unit_offset <= u) lo = mid;
+        else hi = mid;
+    }
+    return lo;
 }
 
 // Stage 2: per-symbol demodulation, persistent grid.  The workgroup stages

@@ -2,7 +2,13 @@
 // re-runs of the frames and symbols they flagged (exact_frame,
 // recheck_frames, settle_frames; k_spec_settle closes the SF 11-12
 // separate launches' speculation) and, in the same launch, the finalisation
-// (k_post).
+// (k_post).  The passes these share are defined once, in lphy_demod.h:
+// workgroup_max (the max-abs reduction), exact_symbol (a symbol with the
+// per-sample Annex G rotation), settle_verdict (the certificate check of a
+// speculatively normalised frame) and, in k_spec_settle, estimate_unit (an
+// estimate symbol: staging, exact FFT, bins kept).  exact_frame and
+// settle_frames hold estimate_unit's pass written out (inside k_post the
+// helper cost registers): a change to it is made there too.
 #pragma once
 #include "lphy_demod.h"
 #include "lphy_final.h"
@@ -21,15 +27,15 @@ template <int SF>
 struct PostShared {
     cf32 lds[Geo<SF>::T * Geo<SF>::SSTRIDE];
     ArgMax red[kTile / 64];
-    UnitResult units[Geo<SF>::T];
-    float upow[Geo<SF>::T];
+    UnitResult units[Geo<SF>::T];  // exact_frame: a chunk's estimate units ...
+    float upow[Geo<SF>::T];        // ... and, osr > 1, their detector powers
     float wmax[kTile / 64];
     lphy_frame_meta m;
     uint16_t sw[2];
     unsigned list[kTile];
     unsigned listf[kTile];
     unsigned count;
-    UnitResult ures2[kTile][2];  // settle_frames: both estimate units of each frame
+    UnitResult ures2[kTile][2];  // settle_frames, k_spec_settle: both estimate units of each listed frame
 };
 
 template <int SF, int MODE>
@@ -41,34 +47,20 @@ __device__ void exact_frame(const DemodArgs& A, unsigned f, PostShared<SF>& sh) 
     const cf32* fr = A.iq + (unsigned long long)f * A.frame_samples;
     const unsigned long long step = (unsigned long long)N * A.osr;
     const bool have_sync = A.total_syms >= 2;
-    // (1) normalisation (modes 1, 2)
+    // (1) normalisation (modes 1, 2; mode 0 keeps mx = 0: scale 1)
+    float mx = 0.0f;
     if (MODE != LPHY_MODE_DEMODULATE) {
         const unsigned long long count = MODE == LPHY_MODE_DECHIRP_LORA_DEMODULATE
                                              ? A.total_syms * N : A.frame_samples;
-        float mx = 0.0f;
         for (unsigned long long i = tid; i < count; i += kTile) {
             cf32 x = fr[i];
             if (MODE == LPHY_MODE_DECHIRP_LORA_DEMODULATE) x = cmul_x(x, A.down[i & (N - 1)]);
             maxabs_acc(mx, x);
         }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const float o = __shfl_xor(mx, off, 64);
-            mx = o > mx ? o : mx;
-        }
-        if ((tid & 63) == 0) sh.wmax[tid >> 6] = mx;
+        mx = workgroup_max(mx, sh.wmax);
     }
-    __syncthreads();
     if (tid == 0) {
-        lphy_frame_meta m{};
-        m.scale = 1.0f;
-        m.have_sync = have_sync;
-        if (MODE != LPHY_MODE_DEMODULATE) {
-            float mx = sh.wmax[0];
-            for (int w = 1; w < kTile / 64; ++w) mx = sh.wmax[w] > mx ? sh.wmax[w] : mx;
-            m = norm_meta(mx, have_sync, A.no_scratch);
-        }
-        sh.m = m;
+        sh.m = norm_meta(mx, have_sync, A.no_scratch);
         sh.sw[0] = sh.sw[1] = 0;
     }
     __syncthreads();
@@ -98,7 +90,7 @@ __device__ void exact_frame(const DemodArgs& A, unsigned f, PostShared<SF>& sh) 
         const ArgMax best = symbol_argmax<SF>(local_argmax<SF>(v, lam), sh.red);
         __syncthreads();
         if (lam == 0) {
-            sh.units[slot] = live ? unit_result<SF>(sh.lds, slot, best) : UnitResult{0, 0, 0.0f, 0.0f, 0};
+            sh.units[slot] = live ? unit_result<SF>(sh.lds, slot, best) : kNoUnit;
             sh.upow[slot] = live && A.osr > 1 ? detector_power(best.v > 0.0f ? best.v : 0.0f, A.power_scale) : 0.0f;
         }
         __syncthreads();
@@ -117,16 +109,7 @@ __device__ void exact_frame(const DemodArgs& A, unsigned f, PostShared<SF>& sh) 
         const unsigned s = s0 + slot;
         const bool live = s < S;
         const SymCtx c = sym_ctx<true>(A, f, live ? s : 0, live, N, m);
-        if (A.win)
-            restage_symbol<SF, MODE | kWinBit, true>(sh.lds, Stage<SF>(slot, lam), fr + c.base, c, lam,
-                                                     A.down, A.win, (unsigned)A.osr);
-        else
-            restage_symbol<SF, MODE, true>(sh.lds, Stage<SF>(slot, lam), fr + c.base, c, lam,
-                                           A.down, nullptr, (unsigned)A.osr);
-        __syncthreads();
-        cf32 v[16];
-        fft_tile<SF, false, true>(v, sh.lds, slot, lam, A.tw);
-        const ArgMax best = symbol_argmax<SF>(local_argmax<SF>(v, lam), sh.red);
+        const ArgMax best = exact_symbol<SF, MODE>(A, fr, c, sh.lds, slot, lam, sh.red);
         if (lam == 0 && live) {
             if (c.have_sync && s < 2) sh.sw[s] = c.ok ? (uint16_t)best.i : (uint16_t)0;
             else if (c.ok) A.syms[(unsigned long long)f * A.out_per_frame + (c.have_sync ? s - 2 : s)] = (uint16_t)best.i;
@@ -238,17 +221,7 @@ __device__ void recheck_frames(const DemodArgs& A, unsigned long long fb, bool m
             lphy_frame_meta m = A.meta[f];
             m.status = 0;
             const SymCtx c = sym_ctx<true>(A, (unsigned)f, sy, live, N, m);
-            const cf32* fr = A.iq + f * A.frame_samples;
-            if (A.win)
-                restage_symbol<SF, MODE | kWinBit, true>(sh.lds, Stage<SF>(slot, lam), fr + c.base, c, lam,
-                                                         A.down, A.win, (unsigned)A.osr);
-            else
-                restage_symbol<SF, MODE, true>(sh.lds, Stage<SF>(slot, lam), fr + c.base, c, lam,
-                                               A.down, nullptr, (unsigned)A.osr);
-            __syncthreads();
-            cf32 v[16];
-            fft_tile<SF, false, true>(v, sh.lds, slot, lam, A.tw);
-            const ArgMax best = symbol_argmax<SF>(local_argmax<SF>(v, lam), sh.red);
+            const ArgMax best = exact_symbol<SF, MODE>(A, A.iq + f * A.frame_samples, c, sh.lds, slot, lam, sh.red);
             if (lam == 0 && live) store_symbol(A, c, (uint16_t)best.i);
             __syncthreads();
         }
@@ -260,13 +233,9 @@ __device__ void recheck_frames(const DemodArgs& A, unsigned long long fb, bool m
 // frame's later samples overturned (status kStatusSettle[Recheck]), among the
 // workgroup's frames fb .. fb + kTile - 1 (thread t: frame fb + t, `mine`).
 // Their two estimate symbols are transformed again, T/2 frames per tile, with
-// the exact normalisation (the reference's arithmetic, as exact_frame), and
-// folded into the exact offsets.  The symbols stand when the time shift is
-// unchanged and every certified symbol's lead still covers the larger sample
-// bound and the rate difference: a rate error d moves every bin by at most
-// |d| N sum|y_i| <= |d| N A (the phase error of sample i is |d| i), charged
-// twice on both sides of the comparison as fast_certified charges its B.
-// Otherwise the frame is re-run whole (kStatusFixup).
+// the exact normalisation (as estimate_unit), and settle_verdict folds them into
+// the exact offsets and decides whether the symbols stand or the frame is
+// re-run whole (kStatusFixup).
 template <int SF, int MODE>
 __device__ void settle_frames(const DemodArgs& A, unsigned long long fb, bool mine, PostShared<SF>& sh) {
     using G = Geo<SF>;
@@ -305,28 +274,9 @@ __device__ void settle_frames(const DemodArgs& A, unsigned long long fb, bool mi
     if ((unsigned)tid < n) {
         const unsigned long long g = fb + sh.list[tid];
         const lphy_frame_meta sm = A.meta[g];
-        lphy_frame_meta e = norm_meta(sm.cfo, true, 0);
-        EstFold fold;
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const UnitResult r = sh.ures2[tid][u];
-            if (r.valid) fold.add(r.idx, r.findex, 0, r.phase);
-            else fold.add(0, 0.0f, 0, 0.0f);
-        }
-        fold.finish(e, 2, N, 1);
-        // amplitude bound of the speculatively scaled samples, and the
-        // smallest bound of any symbol (|start| grows with the symbol)
-        const float a = fmaxf(1.0f, sm.cfo * sm.scale) * 1.0001f;
-        const float b1 = cert_bound<SF>(sm.rate, sm.rate * (float)sm.t_off, 1.0f);
-        const float d = fabsf(e.rate - sm.rate) * (1.0f + 4.0f * kU);
-        const float A1 = (float)N * 1.41421366f * 1.0001f;
-        const bool ok = e.t_off == sm.t_off && sm.t_off >= -N && sm.t_off <= N &&
-                        sm.time_offset > 4.0f * a + 4.0f * d * (float)N * A1 * a / b1;
-        lphy_frame_meta r = e;
-        r.sw0 = sm.sw0;
-        r.sw1 = sm.sw1;
-        r.status = !ok ? kStatusFixup : (sm.status == kStatusSettleRecheck ? kStatusRecheck : 0);
-        A.meta[g] = r;
+        // the record holds {cfo: the max-abs, time_offset: the least certificate ratio}
+        A.meta[g] = settle_verdict<SF>(sm, norm_meta(sm.cfo, true, 0), sh.ures2[tid][0], sh.ures2[tid][1],
+                                       sm.cfo * sm.scale, sm.time_offset, sm.status == kStatusSettleRecheck);
     }
     __syncthreads();
 }
@@ -336,9 +286,9 @@ __device__ void settle_frames(const DemodArgs& A, unsigned long long fb, bool mi
 // estimates of settled frames run in parallel).  The samples no symbol
 // window covers are scanned; the frame's true max-abs then confirms the
 // two-symbol normalisation, or - NaN / inf - sends the frame to k_post's
-// exact re-run, or settles it here: both estimate FFTs again with the exact
-// scale (the reference's arithmetic, as exact_frame) and the certificate
-// check of settle_frames against the exact rate, else the exact re-run.
+// exact re-run, or settles it here as settle_frames does: both estimate
+// units again with the exact scale (estimate_unit), then settle_verdict
+// against the exact rate, else the exact re-run.
 template <int SF, int MODE>
 __global__ __launch_bounds__(kTile) void k_spec_settle(DemodArgs A) {
     using G = Geo<SF>;
@@ -364,16 +314,8 @@ __global__ __launch_bounds__(kTile) void k_spec_settle(DemodArgs A) {
             bad |= !(__builtin_isfinite(x.x) && __builtin_isfinite(x.y));
             maxabs_acc(mx, x);
         }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const float o = __shfl_xor(mx, off, 64);
-            mx = o > mx ? o : mx;
-        }
         fbad = __syncthreads_or(bad);
-        if ((tid & 63) == 0) sh.wmax[tid >> 6] = mx;
-        __syncthreads();
-        frag = sh.wmax[0];
-        for (int w = 1; w < kTile / 64; ++w) frag = sh.wmax[w] > frag ? sh.wmax[w] : frag;
+        frag = workgroup_max(mx, sh.wmax);
     }
     const uint4 r = A.spec_big[f];
     const float mx01 = __uint_as_float(r.x);
@@ -389,44 +331,13 @@ __global__ __launch_bounds__(kTile) void k_spec_settle(DemodArgs A) {
     for (unsigned u0 = 0; u0 < 2; u0 += T) {
         const unsigned s = u0 + (unsigned)slot;
         const bool live = s < 2;
-        const Stage<SF> st(slot, lam);
-#pragma unroll
-        for (int e = 0; e < G::E; ++e) {
-            const int i = lam + e * G::LPS;
-            st.put(sh.lds, e, live ? est_sample(A, fr, (unsigned long long)s * N + (unsigned)i, i, N, me) : czero());
-        }
-        __syncthreads();
-        cf32 v[16];
-        fft_tile<SF, false, true>(v, sh.lds, slot, lam, A.tw);
-#pragma unroll
-        for (int e = 0; e < G::E; ++e) sh.lds[G::addr(slot, bin_of<SF>(e, lam))] = v[e];
-        const ArgMax best = symbol_argmax<SF>(local_argmax<SF>(v, lam), sh.red);
-        __syncthreads();
+        const ArgMax best = estimate_unit<SF>(A, fr, (int)s, 0, 1, me, live, sh.lds, slot, lam, A.tw, sh.red);
         if (lam == 0 && live) sh.ures2[0][s] = unit_result<SF>(sh.lds, slot, best);
         __syncthreads();
     }
-    if (tid == 0) {
-        lphy_frame_meta e = me;
-        EstFold fold;
-        for (int u = 0; u < 2; ++u) {
-            const UnitResult ur = sh.ures2[0][u];
-            if (ur.valid) fold.add(ur.idx, ur.findex, 0, ur.phase);
-            else fold.add(0, 0.0f, 0, 0.0f);
-        }
-        fold.finish(e, 2, N, 1);
-        const float a = fmaxf(1.0f, mt * m.scale) * 1.0001f;
-        const float b1 = cert_bound<SF>(m.rate, m.rate * (float)m.t_off, 1.0f);
-        const float d = fabsf(e.rate - m.rate) * (1.0f + 4.0f * kU);
-        const float A1 = (float)N * 1.41421366f * 1.0001f;
-        const float R = __uint_as_float(r.z);
-        const bool ok = e.t_off == m.t_off && m.t_off >= -N && m.t_off <= N &&
-                        R > 4.0f * a + 4.0f * d * (float)N * A1 * a / b1;
-        lphy_frame_meta out = e;
-        out.sw0 = m.sw0;
-        out.sw1 = m.sw1;
-        out.status = !ok ? kStatusFixup : (((r.w & 2u) || m.status == kStatusRecheck) ? kStatusRecheck : 0);
-        A.meta[f] = out;
-    }
+    if (tid == 0)
+        A.meta[f] = settle_verdict<SF>(m, me, sh.ures2[0][0], sh.ures2[0][1], mt * m.scale, __uint_as_float(r.z),
+                                       (r.w & 2u) || m.status == kStatusRecheck);
 }
 
 // After the symbol kernels: the exact re-run of the frames they flagged

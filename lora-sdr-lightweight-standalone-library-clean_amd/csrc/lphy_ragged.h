@@ -14,7 +14,11 @@
 // get a per-frame view of it (frame_view: base pointers, samples, total_syms,
 // out_per_frame of one frame, frame index 0), so the end clamp, the max-abs
 // extent and the output slots are the frame's own and the uniform kernels are
-// compiled from unchanged code.
+// compiled from unchanged code.  From there: the prologue's max-abs reduction
+// (workgroup_max) and the unit-to-frame search (unit_frame, shared with the
+// ragged transmit, lphy_tx.h).  The prologue's estimate pass is estimate_unit
+// written out (at SF 12 the helper cost registers and a wave per SIMD): a
+// change to it is made here too.
 // Exactness: every product a non-finite value could reach is redone with the
 // reference's Annex G product in place (the max-abs scan and a symbol's
 // staging + FFT), so no frame is handed to a later exact re-run.
@@ -123,24 +127,10 @@ __global__ __launch_bounds__(kTile) void k_rg_prologue(RaggedArgs R) {
             } else {
                 scan([&](cf32 x, unsigned) { maxabs_acc(mx, x); });
             }
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) {
-                const float o = __shfl_xor(mx, off, 64);
-                mx = o > mx ? o : mx;
-            }
         }
-        if ((tid & 63) == 0) wmax[tid >> 6] = mx;
-        __syncthreads();
+        mx = workgroup_max(mx, wmax);  // (0 where nothing was scanned: scale 1)
         if (tid == 0) {
-            lphy_frame_meta m{};
-            m.scale = 1.0f;
-            m.have_sync = total >= 2;
-            if (st == 0 && mode != LPHY_MODE_DEMODULATE) {
-                mx = wmax[0];
-#pragma unroll
-                for (int w = 1; w < kTile / 64; ++w) mx = wmax[w] > mx ? wmax[w] : mx;
-                m = norm_meta(mx, total >= 2, R.A.no_scratch);
-            }
+            lphy_frame_meta m = norm_meta(mx, total >= 2, R.A.no_scratch);
             if (st != 0) {
                 m = lphy_frame_meta{};
                 m.status = st;
@@ -188,7 +178,7 @@ __global__ __launch_bounds__(kTile) void k_rg_prologue(RaggedArgs R) {
         __syncthreads();
         if (lam == 0 && k < FPW) {
             bound_check(u, 2 * FPW);
-            units[u] = live ? unit_result<SF>(lds, slot, best) : UnitResult{0, 0, 0.0f, 0.0f, 0};
+            units[u] = live ? unit_result<SF>(lds, slot, best) : kNoUnit;
         }
     }
     __syncthreads();
@@ -263,15 +253,7 @@ __global__ __launch_bounds__(kTile, SF <= 10 ? 2 : 1) void k_rg_demod(RaggedArgs
             u = ((unsigned long long)hi32 << 32) | lo32;
         }
         bool live = u < units;
-        // unit_offset[lo] <= u < unit_offset[hi] throughout
-        unsigned lo = 0, hi = nframes;
-        if (live) {
-            while (hi - lo > 1) {
-                const unsigned mid = lo + ((hi - lo) >> 1);
-                if (desc[mid].unit_offset <= u) lo = mid;
-                else hi = mid;
-            }
-        }
+        const unsigned lo = live ? unit_frame(desc, nframes, u) : 0u;
         const lphy_ragged_desc d = desc[lo];
         const DemodArgs V = frame_view<SF>(R, lo, d);
         const unsigned long long s64 = u - d.unit_offset;

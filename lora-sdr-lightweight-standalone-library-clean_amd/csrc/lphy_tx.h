@@ -162,16 +162,7 @@ __global__ __launch_bounds__(kTile) void k_tx_samples(TxArgs A, SRC src) {
     for (unsigned long long t0 = (unsigned long long)blockIdx.x * kTile; t0 < units; t0 += stride) {
         const unsigned long long u = t0 + (unsigned)tid;
         bool live = u < units;
-        // unit_offset[lo] <= u < unit_offset[hi] throughout
-        unsigned lo = 0, hi = nframes;
-        if (live) {
-            while (hi - lo > 1) {
-                const unsigned mid = lo + ((hi - lo) >> 1);
-                if (desc[mid].unit_offset <= u) lo = mid;
-                else hi = mid;
-            }
-        }
-        const lphy_ragged_desc d = desc[lo];
+        const lphy_ragged_desc d = desc[live ? unit_frame(desc, nframes, u) : 0u];
         const unsigned long long s = u - d.unit_offset;
         // (a table whose prefix is wrong cannot lead outside the frame; the
         // byte form's odd last symbol is not modulated)
