@@ -96,10 +96,12 @@ struct SfOps {
     int (*estimate)(const DemodArgs&, hipStream_t);
     // debug build: read (and reset) this SF's failed index checks (else null)
     int (*violations)(unsigned long long* out, int reset);
-    // lphy_hip_demod_ragged: prologue, symbols and finalisation (SF 7-12)
-    int (*ragged)(const RaggedArgs&, hipStream_t);
-    // lphy_hip_detect_batch: k_detect (SF 7-12)
-    int (*detect)(const DetectArgs&, hipStream_t);
+    // lphy_hip_demod_ragged: prologue, symbols and finalisation (SF 7-12);
+    // grid_cap > 0 caps the symbol kernel's persistent grid (test build:
+    // lphy_hip_test_grid_cap, else 0)
+    int (*ragged)(const RaggedArgs&, hipStream_t, unsigned grid_cap);
+    // lphy_hip_detect_batch: k_detect (SF 7-12); grid_cap as above
+    int (*detect)(const DetectArgs&, hipStream_t, unsigned grid_cap);
 };
 extern const SfOps sf_ops_1, sf_ops_2, sf_ops_3, sf_ops_4, sf_ops_5, sf_ops_6,
     sf_ops_7, sf_ops_8, sf_ops_9, sf_ops_10, sf_ops_11, sf_ops_12;

@@ -91,6 +91,7 @@ struct lphy_hip_ctx {
     std::atomic<long> fused_min{-1};
     std::atomic<int> mod_force_serial{0};  // (test build: lphy_hip_test_mod_force_serial)
     std::atomic<size_t> pinned_max{kPinnedMax};  // (test build: lphy_hip_test_pinned_max)
+    std::atomic<unsigned> grid_cap{0};  // (test build: lphy_hip_test_grid_cap)
     // (per-call scratch of the device entry points - the SF 11-12 speculation
     // records, the producer's phases, the compensation's shift buffer - comes
     // from the stream-ordered allocator on the caller's stream, so concurrent
@@ -257,6 +258,18 @@ void ctx_args(const lphy_hip_ctx* c, ARGS& A) {
     A.win = c->window == LPHY_WINDOW_HANN ? c->d_win : nullptr;
     A.power_scale = c->power_scale;
     A.counters = c->d_counters;
+}
+
+// Most workgroups the persistent grids of k_rg_demod, k_detect and
+// k_tx_samples get on this context (0: no cap; test build only,
+// lphy_hip_test_grid_cap).
+unsigned test_grid_cap(const lphy_hip_ctx* c) {
+#ifdef LPHY_TEST_PATHS
+    return c->grid_cap.load(std::memory_order_relaxed);
+#else
+    (void)c;
+    return 0;
+#endif
 }
 
 // Counters [first, first + n) of the context after everything on the device
@@ -570,7 +583,7 @@ int demod_ragged_impl(lphy_hip_ctx* c, const float* d_iq, const lphy_ragged_desc
     R.units_hint = units_hint;
     R.shift = (int)c->sf - 4;
     R.decode = (flags & LPHY_F_DECODE) ? 1 : 0;
-    return ops->ragged(R, st);
+    return ops->ragged(R, st, test_grid_cap(c));
 }
 }  // namespace
 
@@ -617,7 +630,7 @@ int detect_impl(lphy_hip_ctx* c, const float* d_iq, size_t total_samples, size_t
     D.step = step;
     D.windows = windows;
     D.dechirp = (flags & LPHY_DET_DECHIRP) ? 1 : 0;
-    return ops->detect(D, st);
+    return ops->detect(D, st, test_grid_cap(c));
 }
 }  // namespace
 
@@ -991,6 +1004,7 @@ int tx_launch(const lphy_hip_ctx* c, SRC src, const lphy_ragged_desc* d_desc, si
     A.sync = sync;
     unsigned grid = tx_resident_grid<SRC>(c->device);
     if (units_hint) grid = (unsigned)std::min<unsigned long long>(grid, (units_hint + kTile - 1) / kTile);
+    if (const unsigned cap = test_grid_cap(c)) grid = std::min(grid, cap);
     hipLaunchKernelGGL(k_tx_walk<SRC>, dim3((unsigned)((frames + 63) / 64)), dim3(64), 0, st, A, src);
     hipLaunchKernelGGL(k_tx_samples<SRC>, dim3(grid), dim3(kTile), 0, st, A, src);
     HIP_OK(hipGetLastError());
@@ -1040,6 +1054,17 @@ int lphy_hip_test_mod_force_serial(lphy_hip_ctx* c, int on) {
 int lphy_hip_test_pinned_max(lphy_hip_ctx* c, size_t bytes) {
     if (!c) return -EINVAL;
     c->pinned_max.store(bytes, std::memory_order_relaxed);
+    return 0;
+}
+
+// Test build only: at most `blocks` workgroups in the persistent grids of
+// k_rg_demod, k_detect and k_tx_samples on this context, after the launchers'
+// own caps (0: the default).  A small call then walks its grid-stride loops
+// more than once, which otherwise needs more tiles than the device holds
+// workgroups.
+int lphy_hip_test_grid_cap(lphy_hip_ctx* c, unsigned blocks) {
+    if (!c) return -EINVAL;
+    c->grid_cap.store(blocks, std::memory_order_relaxed);
     return 0;
 }
 

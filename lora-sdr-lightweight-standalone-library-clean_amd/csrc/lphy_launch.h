@@ -201,11 +201,12 @@ int launch_post_sf(int mode, const DemodArgs& A, const FinalArgs& F, bool fix, b
 // lphy_hip_demod_ragged (lphy_ragged.h), SF 7-12: prologue, symbols,
 // finalisation.  The symbol kernel's persistent grid covers the call's whole
 // symbols when the host knows them (units_hint), else the device (the
-// workgroups past the last unit leave at once).
+// workgroups past the last unit leave at once).  grid_cap > 0 (test build,
+// lphy_hip_test_grid_cap) caps that grid, so each workgroup walks more tiles.
 template <int SF>
-int launch_ragged_sf(const RaggedArgs& R, hipStream_t st) {
+int launch_ragged_sf(const RaggedArgs& R, hipStream_t st, unsigned grid_cap) {
     if constexpr (SF < 7) {
-        (void)R; (void)st;
+        (void)R; (void)st; (void)grid_cap;
         return -ENOTSUP;
     } else {
         using G = Geo<SF>;
@@ -219,6 +220,7 @@ int launch_ragged_sf(const RaggedArgs& R, hipStream_t st) {
                 const unsigned long long tiles = (R.units_hint + G::T - 1) / G::T;
                 if (grid > tiles) grid = tiles;
             }
+            if (grid_cap && grid > grid_cap) grid = grid_cap;
             hipLaunchKernelGGL((k_rg_demod<SF, MODE>), dim3((unsigned)grid), dim3(kTile), 0, st, R);
             return 0;
         });
@@ -229,11 +231,11 @@ int launch_ragged_sf(const RaggedArgs& R, hipStream_t st) {
 }
 
 // lphy_hip_detect_batch (lphy_detect.h), SF 7-12: one persistent launch over
-// tiles of Geo<SF>::T windows.
+// tiles of Geo<SF>::T windows (grid_cap as in launch_ragged_sf).
 template <int SF>
-int launch_detect_sf(const DetectArgs& D, hipStream_t st) {
+int launch_detect_sf(const DetectArgs& D, hipStream_t st, unsigned grid_cap) {
     if constexpr (SF < 7) {
-        (void)D; (void)st;
+        (void)D; (void)st; (void)grid_cap;
         return -ENOTSUP;
     } else {
         auto go = [&](auto p) {
@@ -242,6 +244,7 @@ int launch_detect_sf(const DetectArgs& D, hipStream_t st) {
             unsigned long long grid = (unsigned long long)resident_grid<&k_detect<SF, PREP>>();
             const unsigned long long tiles = (D.windows + T - 1) / T;
             if (grid > tiles) grid = tiles;
+            if (grid_cap && grid > grid_cap) grid = grid_cap;
             hipLaunchKernelGGL((k_detect<SF, PREP>), dim3((unsigned)grid), dim3(kTile), 0, st, D);
         };
         const int prep = (D.dechirp ? kPrepDechirp : 0) | (D.win ? kPrepWindow : 0);

@@ -17,8 +17,8 @@ template int launch_frames_sf<LPHY_SF>(const DemodArgs&, hipStream_t);
 template int launch_wave_sf<LPHY_SF>(const DemodArgs&, hipStream_t);
 template int launch_post_sf<LPHY_SF>(int, const DemodArgs&, const FinalArgs&, bool, bool, hipStream_t);
 template int launch_estimate_sf<LPHY_SF>(const DemodArgs&, hipStream_t);
-template int launch_ragged_sf<LPHY_SF>(const RaggedArgs&, hipStream_t);
-template int launch_detect_sf<LPHY_SF>(const DetectArgs&, hipStream_t);
+template int launch_ragged_sf<LPHY_SF>(const RaggedArgs&, hipStream_t, unsigned);
+template int launch_detect_sf<LPHY_SF>(const DetectArgs&, hipStream_t, unsigned);
 }  // namespace
 
 #ifdef LPHY_DEBUG_BOUNDS

@@ -8,6 +8,18 @@
 // The same holds for the launch overrides below: only the test build reads
 // them from the environment; the product library's dispatch depends on the
 // call's arguments and lphy_hip_ctx_set_fused_min_frames alone.
+//   * lphy_hip_test_grid_cap(ctx, blocks), per context (0 restores the
+//     default): the persistent grids of k_rg_demod, k_detect and k_tx_samples
+//     get min(grid, blocks) workgroups, after the launchers' own caps
+//     (units_hint, the call's tiles).  Those kernels are launched with
+//     min(resident grid, tiles of the call) workgroups, so their grid-stride
+//     loops take a second trip only in a call with more tiles than the device
+//     holds workgroups; under a cap of 1 one workgroup walks every tile, under
+//     a small cap the workgroups make unequal numbers of trips
+//     (tests/test_gpu_persistent_trips.py).  A host-side argument of the
+//     launchers: no kernel reads it, and the product library has neither the
+//     symbol nor the cap.  The uniform kernels (k_wave, k_demod, k_frames)
+//     are outside it: the suite's larger batches walk their grids many times.
 #pragma once
 
 #include <cstdlib>

@@ -636,6 +636,15 @@ class Demodulator:
         fn.argtypes = [_vp, _sz]
         _chk(fn(self.ctx, int(nbytes)), "lphy_hip_test_pinned_max")
 
+    def grid_cap(self, blocks: int) -> None:
+        """Test build only: at most `blocks` workgroups in the persistent grids
+        of the ragged symbol kernel, the detector and the ragged transmit's
+        sample pass on this context (0: the default), so that a small call
+        walks their grid-stride loops more than once."""
+        fn = self.lib.lphy_hip_test_grid_cap
+        fn.argtypes = [_vp, C.c_uint]
+        _chk(fn(self.ctx, int(blocks)), "lphy_hip_test_grid_cap")
+
     def recheck_count(self, reset: bool = True) -> int:
         """Symbols the fused kernel re-ran with the exact rotation (device sync)."""
         n = C.c_ulonglong(0)
