@@ -28,6 +28,8 @@
  *                          over a batch of windows (lphy_detect_rec, below)
  *   lphy_hip_decode_batch  lora_phy::decode / lora_decode on device symbols
  *   lphy_hip_estimate_batch lora_phy::estimate_offsets src/phy/phy.cpp:81-148
+ *   lphy_hip_estimate_ragged the same for frames of different lengths in one
+ *                            call (lphy_ragged_desc, below)
  *   lphy_hip_modulate_batch lora_phy::lora_modulate  src/phy/LoRaMod.cpp:8-43
  *                            (producer; bit-exact, used for synthetic IQ)
  *   lphy_hip_modulate_ragged lora_phy::lora_modulate src/phy/LoRaMod.cpp:8-43
@@ -314,6 +316,61 @@ int lphy_hip_estimate_batch(lphy_hip_ctx* ctx, const float* d_iq,
                             size_t est_samples, lphy_frame_meta* d_meta,
                             void* stream);
 
+/* ------------------------------------------------------------------------
+ * estimate_offsets (phy.cpp:81-148) for every frame of a ragged table in one
+ * launch: the table of lphy_hip_demod_ragged, lphy_hip_compensate_ragged and
+ * the ragged transmit.  What it leaves in d_meta[f].cfo / .time_offset feeds
+ * lphy_hip_compensate_ragged on the same stream, so estimate -> compensate ->
+ * demodulate runs device-resident for frames of different lengths.
+ *
+ * Frame f, with d = d_desc[f] and step = N * osr:
+ *   - its estimate extent is e = min(d.samples, est_samples) samples;
+ *     est_samples == 0 means the whole frame, e = d.samples.  It has n = e /
+ *     step whole symbols.  Nothing of the frame past n * step samples is read
+ *     (neither the partial symbol at the end of the extent nor the rest of
+ *     the frame), and nothing outside the frame.
+ *   - n >= 1: d_meta[f] is rewritten as a whole, as lphy_hip_estimate_batch
+ *     rewrites it: cfo and time_offset bit for bit what estimate_offsets gives
+ *     for those n * step samples alone (a Hann context applies the window,
+ *     phy.cpp:110-111), t_off = (int)round(time_offset), rate = -2*pi*cfo / N,
+ *     status = 0, scale = 1, have_sync = (d.samples / step >= 2), and sw0, sw1,
+ *     sync_word, crc_ok and normalised = 0.
+ *   - n == 0: d_meta[f] is left untouched (phy.cpp:87,91).
+ *   - d.samples >= 2^31: d_meta[f] is all zero but status = -ERANGE, and
+ *     nothing of the frame is read (lphy_hip_demod_ragged's rule).
+ *   - sym_offset and unit_offset are not read, nor is record [frames]
+ *     (unit_offset counts the whole symbols of the whole frame, not the
+ *     estimate's).  Frames may lie in any address order and may overlap each
+ *     other in the IQ: the call only reads it.
+ *
+ * Scope: SF 7-12, every osr the context accepts, window none or Hann.
+ * Returns -EINVAL for a null ctx, then 0 for frames == 0; -EINVAL for a null
+ * d_iq, d_desc or d_meta; -ERANGE for frames >= 2^31; -ENOTSUP for SF < 7.
+ * All of it before any device call.
+ *
+ * The device form is asynchronous on `stream`: one launch, no device
+ * allocation, no host read of the table.  A workgroup takes a group of
+ * consecutive frames (16 at SF 7 ... 1 at SF 11-12) and transforms their
+ * estimate symbols T at a time (T = 32 at SF 7 ... 1 at SF 12), so the
+ * parallelism within one frame is T symbols per workgroup, as in
+ * lphy_hip_estimate_batch: the call is for many frames with short estimate
+ * extents; a single very long buffer is lphy_hip_estimate_host's case.
+ *
+ * The host form goes through the context's stream and staging like
+ * lphy_hip_demod_host.  It checks the table before any device call (-ERANGE
+ * for any samples >= 2^31 or an iq_offset above 2^48; the prefix is not
+ * required), uploads h_iq over the descriptors' extent (the largest iq_offset
+ * + samples), the frames' records and h_meta, and downloads h_meta: the
+ * records of n == 0 frames keep the caller's values.
+ * --------------------------------------------------------------------- */
+int lphy_hip_estimate_ragged(lphy_hip_ctx* ctx, const float* d_iq,
+                             const lphy_ragged_desc* d_desc, size_t frames,
+                             size_t est_samples, lphy_frame_meta* d_meta,
+                             void* stream);
+int lphy_hip_estimate_ragged_host(lphy_hip_ctx* ctx, const float* h_iq,
+                                  const lphy_ragged_desc* h_desc, size_t frames,
+                                  size_t est_samples, lphy_frame_meta* h_meta);
+
 /* compensate_offsets (phy.cpp:150-180), in place on one device buffer. */
 int lphy_hip_compensate(lphy_hip_ctx* ctx, float* d_iq, size_t count,
                         float cfo, float time_offset, void* stream);
@@ -321,8 +378,9 @@ int lphy_hip_compensate(lphy_hip_ctx* ctx, float* d_iq, size_t count,
 /* ------------------------------------------------------------------------
  * compensate_offsets (phy.cpp:150-180) for every frame of a batch, each with
  * its own offsets read on the device from d_meta[f].cfo / .time_offset: what
- * lphy_hip_estimate_batch left there feeds it on the same stream, with no
- * host copy between the two calls.  Only those two fields are read (not
+ * lphy_hip_estimate_batch (or, for the ragged form, lphy_hip_estimate_ragged)
+ * left there feeds it on the same stream, with no host copy between the two
+ * calls.  Only those two fields are read (not
  * .rate, which is -2*pi*cfo/N without osr, nor .t_off: a caller may have
  * filled cfo and time_offset alone); d_meta is not written.
  *

@@ -102,6 +102,9 @@ struct SfOps {
     int (*ragged)(const RaggedArgs&, hipStream_t, unsigned grid_cap);
     // lphy_hip_detect_batch: k_detect (SF 7-12); grid_cap as above
     int (*detect)(const DetectArgs&, hipStream_t, unsigned grid_cap);
+    // lphy_hip_estimate_ragged: k_rg_estimate (SF 7-12); of RaggedArgs it
+    // reads A's tables, iq, meta, frames, osr and desc
+    int (*estimate_ragged)(const RaggedArgs&, unsigned long long est_samples, hipStream_t);
 };
 extern const SfOps sf_ops_1, sf_ops_2, sf_ops_3, sf_ops_4, sf_ops_5, sf_ops_6,
     sf_ops_7, sf_ops_8, sf_ops_9, sf_ops_10, sf_ops_11, sf_ops_12;

@@ -703,6 +703,43 @@ int lphy_hip_estimate_batch(lphy_hip_ctx* c, const float* d_iq, size_t frames,
 }
 
 namespace {
+// The argument checks of both forms of the ragged estimate, in the header's
+// order (before any device call): 0 to go on, 1 when there is nothing to do,
+// or the error.
+int estimate_ragged_check(const lphy_hip_ctx* c, const void* iq, const void* desc, size_t frames, const void* meta) {
+    if (!c) return -EINVAL;
+    if (frames == 0) return 1;
+    if (!iq || !desc || !meta) return -EINVAL;
+    if (frames > 0x7fffffffULL) return -ERANGE;
+    if (c->sf < 7) return -ENOTSUP;
+    return 0;
+}
+
+int estimate_ragged_impl(lphy_hip_ctx* c, const float* d_iq, const lphy_ragged_desc* d_desc, size_t frames,
+                         size_t est_samples, lphy_frame_meta* d_meta, hipStream_t st) {
+    const SfOps* ops = sf_ops(c->sf);
+    if (!ops || !ops->estimate_ragged) return -ENOTSUP;  // (an experiment build without this SF's object)
+    HIP_OK(hipSetDevice(c->device));
+    RaggedArgs R{};
+    DemodArgs& A = R.A;
+    ctx_args(c, A);
+    A.iq = reinterpret_cast<const cf32*>(d_iq);
+    A.meta = d_meta;
+    A.frames = frames;
+    A.osr = (int)c->osr;
+    A.mode = LPHY_MODE_DEMODULATE;
+    R.desc = d_desc;
+    return ops->estimate_ragged(R, (unsigned long long)est_samples, st);
+}
+}  // namespace
+
+int lphy_hip_estimate_ragged(lphy_hip_ctx* c, const float* d_iq, const lphy_ragged_desc* d_desc, size_t frames,
+                             size_t est_samples, lphy_frame_meta* d_meta, void* stream) {
+    if (int rc = estimate_ragged_check(c, d_iq, d_desc, frames, d_meta)) return rc > 0 ? 0 : rc;
+    return estimate_ragged_impl(c, d_iq, d_desc, frames, est_samples, d_meta, (hipStream_t)stream);
+}
+
+namespace {
 // compensate_offsets (phy.cpp:150-180) on device samples.  The rotation is
 // elementwise and runs in place; only a time shift needs scratch (`lent`,
 // when given, is count complex values the caller owns).

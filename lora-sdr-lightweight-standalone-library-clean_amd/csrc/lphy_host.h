@@ -28,7 +28,7 @@ int ensure_host_stage(lphy_hip_ctx* c, size_t bytes) {
 //
 // kMirror: demod, decode and modulate (the per-packet calls of the lora_phy::
 // API) go through the pinned mirror when their copied slices fit
-// it, one DMA copy each way; the other six copy slice by slice from and to
+// it, one DMA copy each way; the other seven copy slice by slice from and to
 // the caller's memory.  Which call does which is a measured choice, not an
 // accident of this code.
 enum HostCopy { kPageable, kMirror };
@@ -195,6 +195,20 @@ int lphy_hip_estimate_host(lphy_hip_ctx* c, const float* h_iq, size_t count,
     if (int rc = hc.begin(estimate_plan(count), {h_iq, h_meta})) return rc;
     return hc.finish(lphy_hip_estimate_batch(c, hc.dev<float>(0), 1, count, count, hc.dev<lphy_frame_meta>(1),
                                              hc.stream()));
+}
+
+// The ragged estimate on host buffers: the descriptors' IQ extent, the
+// frames' records and the caller's h_meta in, one launch, h_meta out (the
+// record of a frame without a whole symbol comes back as it went).
+int lphy_hip_estimate_ragged_host(lphy_hip_ctx* c, const float* h_iq, const lphy_ragged_desc* h_desc, size_t frames,
+                                  size_t est_samples, lphy_frame_meta* h_meta) {
+    if (int rc = estimate_ragged_check(c, h_iq, h_desc, frames, h_meta)) return rc > 0 ? 0 : rc;
+    uint64_t iq_samples = 0;
+    if (int rc = estimate_ragged_extent(h_desc, frames, &iq_samples)) return rc;
+    HostCall hc(c, kPageable);
+    if (int rc = hc.begin(estimate_ragged_plan(iq_samples, frames), {h_iq, h_desc, h_meta})) return rc;
+    return hc.finish(estimate_ragged_impl(c, hc.dev<float>(0), hc.dev<lphy_ragged_desc>(1), frames, est_samples,
+                                          hc.dev<lphy_frame_meta>(2), hc.stream()));
 }
 
 int lphy_hip_compensate_host(lphy_hip_ctx* c, float* h_iq, size_t count, float cfo,

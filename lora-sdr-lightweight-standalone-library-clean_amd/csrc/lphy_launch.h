@@ -266,4 +266,20 @@ int launch_estimate_sf(const DemodArgs& A, hipStream_t st) {
     HIP_OK(hipGetLastError());
     return 0;
 }
+
+// lphy_hip_estimate_ragged (lphy_ragged.h), SF 7-12: one launch, a workgroup
+// per group of FPW frames (k_rg_prologue's grouping).
+template <int SF>
+int launch_estimate_ragged_sf(const RaggedArgs& R, unsigned long long est_samples, hipStream_t st) {
+    if constexpr (SF < 7) {
+        (void)R; (void)est_samples; (void)st;
+        return -ENOTSUP;
+    } else {
+        constexpr int FPW = Geo<SF>::T >= 2 ? Geo<SF>::T / 2 : 1;
+        hipLaunchKernelGGL(k_rg_estimate<SF>, dim3((unsigned)((R.A.frames + FPW - 1) / FPW)), dim3(kTile), 0, st, R,
+                           est_samples);
+        HIP_OK(hipGetLastError());
+        return 0;
+    }
+}
 }  // namespace

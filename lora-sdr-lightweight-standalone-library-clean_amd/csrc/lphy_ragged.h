@@ -22,6 +22,8 @@
 // Exactness: every product a non-finite value could reach is redone with the
 // reference's Annex G product in place (the max-abs scan and a symbol's
 // staging + FFT), so no frame is handed to a later exact re-run.
+// Also lphy_hip_estimate_ragged, on the same table: k_rg_estimate<SF>, one
+// launch, estimate_offsets (phy.cpp:81-148) on each frame's first symbols.
 #pragma once
 #include "lphy_demod.h"
 #include "lphy_final.h"
@@ -329,6 +331,133 @@ __global__ __launch_bounds__(kTile) void k_rg_final(RaggedArgs R) {
     F.decode = R.decode;
     F.set_sync = 1;
     finalize_frame(F, 0);
+}
+
+// ---------------------------------------------------------------------------
+// lphy_hip_estimate_ragged: estimate_offsets (phy.cpp:81-148) on the first
+// n_f = min(samples, est_samples) / (N osr) whole symbols of every frame
+// (est_samples == 0: the whole frame).  k_estimate's packed form (several
+// short frames in a tile) and its unpacked form (one long frame in chunks of
+// T) as one loop: a workgroup takes the prologue's group of FPW consecutive
+// frames and walks their concatenated units, U_f = n_f osr each, in passes of
+// T; a pass may hold the tail of one frame, whole frames and the head of the
+// next.  Thread k folds the units of frame k that lay in the pass, in unit
+// order, and carries the fold across passes (EstFold keeps the state between
+// the osr phases of a symbol, so a pass edge may split them).  The table's
+// unit_offset counts the whole symbols of the whole frame, not these units,
+// and is not read; nor are sym_offset and record [frames].
+// In-frame parallelism is T units per pass per workgroup, as in k_estimate.
+// ---------------------------------------------------------------------------
+template <int SF>
+__global__ __launch_bounds__(kTile) void k_rg_estimate(RaggedArgs R, unsigned long long est_samples) {
+    using G = Geo<SF>;
+    constexpr int N = G::N, T = G::T;
+    constexpr int FPW = T >= 2 ? T / 2 : 1;
+    __shared__ cf32 lds[T * G::SSTRIDE];
+    __shared__ cf32 twl[N];
+    __shared__ ArgMax red[kTile / 64];
+    __shared__ UnitResult units[T];
+    __shared__ float upow[T];
+    __shared__ unsigned long long fiq[FPW];  // the frame's first sample
+    __shared__ unsigned upre[FPW + 1];       // exclusive prefix of the group's units (< FPW 2^31 / N)
+
+    const int tid = threadIdx.x;
+    const int osr = R.A.osr;
+    const unsigned step = (unsigned)N * (unsigned)osr;
+    const unsigned long long nframes = R.A.frames;
+    const unsigned long long f0 = (unsigned long long)blockIdx.x * FPW;
+    for (int i = tid; i < N; i += kTile) twl[i] = R.A.tw[i];
+
+    // (1) the frame of thread k < FPW: status, estimate symbols, units
+    int st = 0;
+    unsigned nsym = 0;       // n_f
+    bool have_sync = false;
+    const bool mine = tid < FPW && f0 + tid < nframes;
+    if (tid < FPW) {
+        unsigned long long off = 0;
+        if (mine) {
+            const lphy_ragged_desc d = R.desc[f0 + tid];
+            if (d.samples >= 0x80000000ull) {
+                st = -ERANGE;  // the ragged demodulator's rule (length_status)
+            } else {
+                const unsigned long long e = est_samples && est_samples < d.samples ? est_samples : d.samples;
+                nsym = (unsigned)e / step;
+                have_sync = (unsigned)d.samples / step >= 2;
+                off = d.iq_offset;
+            }
+        }
+        fiq[tid] = off;
+        upre[tid + 1] = nsym * (unsigned)osr;  // the count; thread 0 makes it the prefix
+    }
+    __syncthreads();
+    if (tid == 0) {
+        unsigned acc = 0;
+        upre[0] = 0;
+        for (int k = 1; k <= FPW; ++k) {
+            acc += upre[k];
+            upre[k] = acc;
+        }
+    }
+    __syncthreads();
+    const unsigned total = upre[FPW];  // uniform
+    const unsigned ubeg = tid < FPW ? upre[tid] : 0u, uend = tid < FPW ? upre[tid + 1] : 0u;
+
+    // (2) passes of T units; (3) the folds of the frames a pass touched
+    EstFold fold;
+    lphy_frame_meta none{};
+    none.scale = 1.0f;
+    const int slot = tid / G::LPS, lam = tid % G::LPS;
+    for (unsigned p0 = 0; p0 < total; p0 += T) {
+        const unsigned u = p0 + (unsigned)slot;
+        const bool live = u < total;
+        int k = 0;  // the last frame whose prefix is <= u: the one that holds it
+        if (live) {
+#pragma unroll
+            for (int j = 1; j < FPW; ++j) k = upre[j] <= u ? j : k;
+        }
+        const unsigned uf = live ? u - upre[k] : 0u;
+        const int s = (int)(uf / (unsigned)osr), t = (int)(uf % (unsigned)osr);
+        DemodArgs V = R.A;  // (mode 0: est_sample reads A.mode and A.win)
+        V.iq = R.A.iq + fiq[k];
+        V.frames = 1;
+        V.frame_samples = (unsigned long long)(upre[k + 1] - upre[k]) * (unsigned)N;  // n_f step: the extent read
+        if (live) {
+            bound_check(k, FPW);
+#pragma unroll
+            for (int e = 0; e < G::E; ++e)
+                iq_check(V, 0, (long long)(((unsigned long long)s * N + (unsigned)(lam + e * G::LPS)) * osr + t));
+        }
+        __syncthreads();  // the previous pass's readers are done with lds / units
+        const ArgMax best = estimate_unit<SF>(V, V.iq, s, t, osr, none, live, lds, slot, lam, twl, red);
+        if (lam == 0) {
+            bound_check(slot, T);
+            units[slot] = live ? unit_result<SF>(lds, slot, best) : kNoUnit;
+            if (osr > 1) upow[slot] = live ? detector_power(best.v > 0.0f ? best.v : 0.0f, R.A.power_scale) : 0.0f;
+        }
+        __syncthreads();
+        if (tid < FPW) {
+            const unsigned a = ubeg > p0 ? ubeg : p0;
+            const unsigned b = uend < p0 + T ? uend : p0 + T;
+            for (unsigned j = a; j < b; ++j) {
+                bound_check((long long)(j - p0), T);
+                fold.unit(units[j - p0], osr > 1 ? upow[j - p0] : 0.0f, osr, false);  // phy.cpp:106-121: no tie-break
+            }
+        }
+    }
+
+    // (4) publish; a frame without a whole symbol keeps its record (phy.cpp:87,91)
+    if (mine) {
+        lphy_frame_meta m{};
+        if (st != 0) {
+            m.status = st;
+            R.A.meta[f0 + tid] = m;
+        } else if (nsym != 0) {
+            m.scale = 1.0f;
+            m.have_sync = have_sync;
+            fold.finish(m, (int)nsym, N, osr);
+            R.A.meta[f0 + tid] = m;
+        }
+    }
 }
 
 }  // namespace

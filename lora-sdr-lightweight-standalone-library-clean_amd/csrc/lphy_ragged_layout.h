@@ -70,6 +70,21 @@ inline int ragged_extent(uint64_t step, const lphy_ragged_desc* h_desc, size_t f
     return 0;
 }
 
+// A caller's table for lphy_hip_estimate_ragged_host: the limits of
+// ragged_extent on the two fields that call reads (iq_offset, samples) and the
+// extent of the IQ they name.  No prefix check: unit_offset is not read.
+inline int estimate_ragged_extent(const lphy_ragged_desc* h_desc, size_t frames, uint64_t* iq_samples) {
+    uint64_t iq = 0;
+    for (size_t f = 0; f < frames; ++f) {
+        const lphy_ragged_desc& d = h_desc[f];
+        if (d.samples >= kRaggedMaxSamples) return -ERANGE;
+        if (d.iq_offset > (uint64_t(1) << 48)) return -ERANGE;
+        if (d.iq_offset + d.samples > iq) iq = d.iq_offset + d.samples;
+    }
+    *iq_samples = iq;
+    return 0;
+}
+
 // lphy_hip_tx_layout: the table of frames that carry h_len_bytes[f] payload
 // bytes each, (2 len + 2) symbols of `step` samples, as ragged_layout packs
 // them in mode 1 - so sym_offset / 2 is the exclusive prefix of len and the

@@ -19,6 +19,7 @@ template int launch_post_sf<LPHY_SF>(int, const DemodArgs&, const FinalArgs&, bo
 template int launch_estimate_sf<LPHY_SF>(const DemodArgs&, hipStream_t);
 template int launch_ragged_sf<LPHY_SF>(const RaggedArgs&, hipStream_t, unsigned);
 template int launch_detect_sf<LPHY_SF>(const DetectArgs&, hipStream_t, unsigned);
+template int launch_estimate_ragged_sf<LPHY_SF>(const RaggedArgs&, unsigned long long, hipStream_t);
 }  // namespace
 
 #ifdef LPHY_DEBUG_BOUNDS
@@ -52,6 +53,7 @@ const SfOps LPHY_CAT(sf_ops_, LPHY_SF) = {
 #endif
     &launch_ragged_sf<LPHY_SF>,
     &launch_detect_sf<LPHY_SF>,
+    &launch_estimate_ragged_sf<LPHY_SF>,
 };
 }  // namespace lphy
 #endif

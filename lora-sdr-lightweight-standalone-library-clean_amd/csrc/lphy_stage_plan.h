@@ -61,7 +61,7 @@ struct StagePlan {
 constexpr size_t kIqBytes = 2 * sizeof(float);  // one complex sample
 constexpr size_t kMetaBytes = sizeof(lphy_frame_meta);
 
-// The plans of the nine *_host entry points, slices in the order named.
+// The plans of the ten *_host entry points, slices in the order named.
 
 // iq | syms | bytes | meta | spec (the SF 11-12 speculation records); `per`:
 // lphy_hip_syms_per_frame
@@ -130,9 +130,20 @@ inline StagePlan tx_plan(size_t in_bytes, size_t frames, size_t iq_samples, size
         .add(out_syms * sizeof(uint16_t), sym_gaps ? kStageInOut : kStageOut);
 }
 
+// iq | desc (the frames' records; record [frames] is not read) | meta
+// (lphy_hip_estimate_ragged_host).  The caller's records go in, so that a
+// frame the call leaves alone comes back as it went.
+inline StagePlan estimate_ragged_plan(size_t iq_samples, size_t frames) {
+    return StagePlan()
+        .add(iq_samples * kIqBytes, kStageIn)
+        .add(frames * sizeof(lphy_ragged_desc), kStageIn)
+        .add(frames * kMetaBytes, kStageInOut);
+}
+
 // Staging every *_host entry point needs for calls of up to `frames` frames
 // of `frame_samples` samples, or one buffer of frames * frame_samples: the
-// largest of the nine plans at that shape.  Demodulation in modes 1/2, which
+// largest of the ten plans at that shape (the ragged estimate's slices are
+// among the ragged demodulator's, so it never sets the size).  Demodulation in modes 1/2, which
 // give no fewer symbols than mode 0; ragged frames of frame_samples each; one
 // detector window per N samples of the buffer; all the frames' symbols in one
 // decode; ragged transmit frames of frame_samples each, gaps or not (the
@@ -146,6 +157,7 @@ inline size_t host_stage_bytes(size_t N, size_t osr, size_t frames, size_t frame
                      detect_plan(n, n / N).end,
                      decode_plan(frames * (total + 2)).end,
                      estimate_plan(n).end,
+                     estimate_ragged_plan(n, frames).end,
                      compensate_plan(n).end,
                      compensate_batch_plan(frames, frame_samples).end,
                      modulate_plan(step, total, mod_scratch).end,

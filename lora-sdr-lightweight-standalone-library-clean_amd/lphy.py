@@ -110,6 +110,7 @@ EXPORTS = (
     "lphy_hip_detect_batch", "lphy_hip_detect_host", "lphy_hip_detect_serial_count",
     "lphy_hip_compensate_batch", "lphy_hip_compensate_ragged", "lphy_hip_compensate_batch_host",
     "lphy_hip_modulate_ragged", "lphy_hip_tx_ragged", "lphy_hip_tx_ragged_host", "lphy_hip_tx_layout",
+    "lphy_hip_estimate_ragged", "lphy_hip_estimate_ragged_host",
 )
 
 WHITEN_SX1232, WHITEN_SX1272, WHITEN_SX1272_LFSR = 0, 1, 2
@@ -171,6 +172,8 @@ def load(path: Path | None = None) -> C.CDLL:
     L.lphy_hip_detect_serial_count.argtypes = [_vp, C.POINTER(C.c_ulonglong), C.c_int]
     L.lphy_hip_decode_batch.argtypes = [_vp, _vp, _sz, _sz, _vp, _vp, _vp]
     L.lphy_hip_estimate_batch.argtypes = [_vp, _vp, _sz, _sz, _sz, _vp, _vp]
+    L.lphy_hip_estimate_ragged.argtypes = [_vp, _vp, _vp, _sz, _sz, _vp, _vp]
+    L.lphy_hip_estimate_ragged_host.argtypes = [_vp, _vp, _vp, _sz, _sz, _vp]
     L.lphy_hip_compensate.argtypes = [_vp, _vp, _sz, C.c_float, C.c_float, _vp]
     L.lphy_hip_compensate_batch.argtypes = [_vp, _vp, _vp, _sz, _sz, _vp, _vp]
     L.lphy_hip_compensate_ragged.argtypes = [_vp, _vp, _vp, _vp, _sz, _vp, _vp]
@@ -483,6 +486,23 @@ class Demodulator:
                                               p_meta, stream),
              "lphy_hip_estimate_batch")
 
+    def estimate_ragged(self, iq, desc, frames, est_samples, meta, stream=None, iq_samples=None):
+        """The same for frames of different lengths in one launch: frame f is
+        desc[f]["samples"] samples at desc[f]["iq_offset"], its estimate runs
+        over the whole symbols of its first min(samples, est_samples) samples
+        (est_samples = 0: the whole frame) and rewrites meta[f]; a frame
+        without a whole symbol there keeps its record
+        (lphy_hip_estimate_ragged).  `desc`: device tensor of
+        RAGGED_DESC_DTYPE records; record [frames] is not read.  iq_samples:
+        the extent the descriptors span (checked against the tensor).
+        Asynchronous."""
+        dv = self.device
+        p_iq = _dev_buf(iq, "iq", dv, (iq_samples or 0) * 8, None)
+        p_desc = _dev_buf(desc, "desc", dv, frames * 32, None)
+        p_meta = _dev_buf(meta, "meta", dv, frames * 32, None)
+        _chk(self.lib.lphy_hip_estimate_ragged(self.ctx, p_iq, p_desc, frames, est_samples, p_meta, stream),
+             "lphy_hip_estimate_ragged")
+
     def compensate_batch(self, iq_in, iq_out, frames, frame_samples, meta, stream=None):
         """compensate_offsets on each of `frames` device frames with the frame's
         own meta[f].cfo / .time_offset, read on the device
@@ -565,6 +585,35 @@ class Demodulator:
         _chk(self.lib.lphy_hip_estimate_host(self.ctx, iq.ctypes.data, iq.size,
                                              meta.ctypes.data), "lphy_hip_estimate_host")
         return meta[0]
+
+    def estimate_ragged_host(self, iq_flat: np.ndarray, lengths_or_desc, est_samples: int = 0, meta=None):
+        """estimate_offsets for frames of different lengths in one call.
+        `lengths_or_desc` is a list of sample counts (frames packed back to
+        back in `iq_flat`) or a RAGGED_DESC_DTYPE array of frames + 1 records
+        (only iq_offset and samples of the first `frames` are read).  `meta`:
+        the caller's `frames` META_DTYPE records, which go in and come back (a
+        frame without a whole symbol in its estimate extent keeps its record);
+        zeros when None.  Returns (meta, desc)."""
+        a = np.asarray(lengths_or_desc)
+        desc = (np.ascontiguousarray(a) if a.dtype == RAGGED_DESC_DTYPE
+                else self.ragged_layout(a, MODE_DEMODULATE))
+        frames = desc.size - 1
+        iq = np.ascontiguousarray(iq_flat, np.complex64).reshape(-1)
+        d = desc[:-1]
+        n_iq = int((d["iq_offset"] + d["samples"]).max()) if d.size else 0
+        if iq.size < n_iq:
+            raise ValueError(f"iq: {iq.size} samples, the descriptors span {n_iq}")
+        m = (np.zeros(frames, META_DTYPE) if meta is None
+             else np.array(meta, META_DTYPE, copy=True).reshape(-1))
+        if m.size != frames:
+            raise ValueError(f"meta: {m.size} records for {frames} frames")
+        pad = np.zeros(1, np.complex64)
+        mpad = np.zeros(1, META_DTYPE)
+        _chk(self.lib.lphy_hip_estimate_ragged_host(self.ctx, (iq if iq.size else pad).ctypes.data,
+                                                    desc.ctypes.data, frames, est_samples,
+                                                    (m if m.size else mpad).ctypes.data),
+             "lphy_hip_estimate_ragged_host")
+        return m, desc
 
     def compensate_host(self, iq: np.ndarray, cfo: float, time_offset: float):
         x = np.array(iq, np.complex64, copy=True).reshape(-1)
