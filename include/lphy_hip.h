@@ -26,6 +26,8 @@
  *                          in one call (lphy_ragged_desc, below)
  *   lphy_hip_detect_batch  LoRaDetector<float>::detect include/lora_phy/LoRaDetector.hpp:39-74
  *                          over a batch of windows (lphy_detect_rec, below)
+ *   lphy_hip_detect_ragged the same on every whole symbol of every frame of
+ *                          a ragged table (lphy_ragged_desc, below)
  *   lphy_hip_decode_batch  lora_phy::decode / lora_decode on device symbols
  *   lphy_hip_estimate_batch lora_phy::estimate_offsets src/phy/phy.cpp:81-148
  *   lphy_hip_estimate_ragged the same for frames of different lengths in one
@@ -254,7 +256,8 @@ int lphy_hip_demod_ragged_host(lphy_hip_ctx* ctx, const float* h_iq,
  * No normalisation, no rotation.  hop < N makes the windows overlap (a
  * sliding detector); step is the decimation: hop = 1, step = osr, windows =
  * osr are the reference's osr phases of one symbol.  A frame's per-symbol SNR
- * is power - power_avg with first = the frame's start, hop = N, step = 1.
+ * is power - power_avg with first = the frame's start, hop = N, step = 1
+ * (for many frames of different lengths: lphy_hip_detect_ragged, below).
  *
  * Every record holds what detect() returns for that input, bit for bit
  * (where the reference gives a NaN, a NaN): an all-zero window gives index
@@ -290,6 +293,61 @@ int lphy_hip_detect_host(lphy_hip_ctx* ctx, const float* h_iq, size_t total_samp
                          size_t first, size_t hop, size_t step, size_t windows,
                          lphy_detect_rec* h_out, unsigned flags);
 int lphy_hip_detect_serial_count(lphy_hip_ctx* ctx, unsigned long long* out, int reset);
+
+/* ------------------------------------------------------------------------
+ * The detector on every whole symbol of every frame of a ragged table, in one
+ * launch: the table of lphy_hip_demod_ragged, lphy_hip_estimate_ragged and
+ * lphy_hip_compensate_ragged.  One lphy_detect_rec per symbol, so a frame's
+ * per-symbol SNR (power - power_avg) comes with its demodulation, whatever
+ * the frames' lengths.
+ *
+ * Frame f, with d = d_desc[f], step = N * osr and n = d.samples / step whole
+ * symbols:
+ *   - symbol s < n feeds the detector x_i = iq[d.iq_offset + s*step + phase +
+ *     i*osr], i = 0..N-1: `phase` < osr picks the decimation phase (0 is what
+ *     demodulate reads, phy.cpp:225).  The input is prepared as
+ *     lphy_hip_detect_batch prepares a window: with LPHY_DET_DECHIRP times
+ *     down[i], on a Hann context times win[i], no normalisation, no rotation.
+ *   - its record goes to d_out[d.unit_offset + s], bit for bit what detect()
+ *     returns for that input: what lphy_hip_detect_batch(first = d.iq_offset +
+ *     phase, hop = step, step = osr, windows = n) gives for the frame alone.
+ *     d_out holds d_desc[frames].unit_offset records (read on the device).
+ *   - the partial symbol at the frame's end is not read, nor anything outside
+ *     the frame, nor sym_offset.
+ *   - n == 0: the frame writes nothing.  d.samples >= 2^31: the frame writes
+ *     nothing and nothing of it is read (lphy_hip_demod_ragged's rule).
+ *   - a table whose unit_offset prefix is wrong cannot lead outside a frame
+ *     or past d_desc[frames].unit_offset records; which records it fills is
+ *     then unspecified.  Frames may lie in any address order and may overlap
+ *     each other in the IQ: the call only reads it.
+ *
+ * Scope: SF 7-12, every osr the context accepts, window none or Hann.
+ * Returns -EINVAL for a null ctx, then 0 for frames == 0; -EINVAL for a null
+ * d_iq, d_desc or d_out, an unknown flag bit or phase >= osr; -ERANGE for
+ * frames >= 2^31; -ENOTSUP for SF < 7.  All of it before any device call.
+ *
+ * The device form is asynchronous on `stream`: one launch, no device
+ * allocation, no host read of the table.  Windows that take the in-order
+ * power_avg walk count in lphy_hip_detect_serial_count, as for
+ * lphy_hip_detect_batch.
+ *
+ * The host form goes through the context's stream and staging like
+ * lphy_hip_demod_host.  It checks the table before any device call: -ERANGE
+ * for any samples >= 2^31, an iq_offset above 2^48 or 2^32 or more whole
+ * symbols, -EINVAL for a unit_offset that is not the exclusive prefix of
+ * samples / step (record [frames] included), as lphy_hip_demod_ragged_host.
+ * It uploads h_iq over the descriptors' extent (the largest iq_offset +
+ * samples) and the frames + 1 records, and downloads h_desc[frames]
+ * .unit_offset records into h_out: every one has exactly one owner.
+ * --------------------------------------------------------------------- */
+int lphy_hip_detect_ragged(lphy_hip_ctx* ctx, const float* d_iq,
+                           const lphy_ragged_desc* d_desc, size_t frames,
+                           unsigned phase, lphy_detect_rec* d_out,
+                           unsigned flags, void* stream);
+int lphy_hip_detect_ragged_host(lphy_hip_ctx* ctx, const float* h_iq,
+                                const lphy_ragged_desc* h_desc, size_t frames,
+                                unsigned phase, lphy_detect_rec* h_out,
+                                unsigned flags);
 
 /* Hamming(8,4)sx decode + sx1272 CRC of device symbols: frame f holds
  * syms_per_frame symbols at d_syms + f*syms_per_frame and yields

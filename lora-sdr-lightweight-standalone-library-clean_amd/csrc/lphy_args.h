@@ -87,6 +87,18 @@ struct DetectArgs {
     unsigned long long* counters;  // ctx counters (kCtrDetectSerial)
 };
 
+// lphy_hip_detect_ragged (lphy_detect.h): symbol s of frame f feeds the
+// detector iq[desc[f].iq_offset + s * N * osr + phase + i * osr], record
+// out[desc[f].unit_offset + s].  Of D it reads the tables, iq, out,
+// power_scale and counters (and the launcher dechirp).
+struct DetectRaggedArgs {
+    DetectArgs D;
+    const lphy_ragged_desc* desc;  // frames + 1 records
+    unsigned frames;               // < 2^31
+    unsigned osr, phase;           // phase < osr
+    unsigned long long units_hint; // whole symbols of the call when the host knows them, else 0
+};
+
 // Per-SF launch entry points (one table per lphy_sf.hip instance)
 struct SfOps {
     int (*demod)(const DemodArgs&, hipStream_t, bool prologue, bool symbols, int per_cu);
@@ -105,6 +117,8 @@ struct SfOps {
     // lphy_hip_estimate_ragged: k_rg_estimate (SF 7-12); of RaggedArgs it
     // reads A's tables, iq, meta, frames, osr and desc
     int (*estimate_ragged)(const RaggedArgs&, unsigned long long est_samples, hipStream_t);
+    // lphy_hip_detect_ragged: k_detect_ragged (SF 7-12); grid_cap as above
+    int (*detect_ragged)(const DetectRaggedArgs&, hipStream_t, unsigned grid_cap);
 };
 extern const SfOps sf_ops_1, sf_ops_2, sf_ops_3, sf_ops_4, sf_ops_5, sf_ops_6,
     sf_ops_7, sf_ops_8, sf_ops_9, sf_ops_10, sf_ops_11, sf_ops_12;

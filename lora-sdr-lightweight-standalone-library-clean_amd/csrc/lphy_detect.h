@@ -36,6 +36,12 @@
 // window whose sum is not finite) the team's first lane walks the slot's bins
 // in order and restates the reference loop literally; each such window counts
 // in the context's kCtrDetectSerial (lphy_hip_detect_serial_count).
+//
+// lphy_hip_detect_ragged is the same detector on every whole symbol of every
+// frame of a lphy_ragged_desc table: k_detect_ragged<SF, PREP> finds each
+// team's window from the table (unit_frame, as k_rg_demod) instead of the
+// lattice.  What follows per window is one function, detect_window, which both
+// kernels call.
 #pragma once
 #include "lphy_demod.h"
 
@@ -61,6 +67,115 @@ __device__ __attribute__((noinline)) float detect_walk(const cf32* lds, int slot
     return (float)(total - (double)max_value);
 }
 
+// One window of one team, all four outputs: what k_detect and
+// k_detect_ragged do per tile once each team knows its window.  The team's
+// window is the N samples iq[base + i * step]; its record goes to out[w].  A
+// team that is not `live` stages zeros and writes nothing.  Every thread of
+// the workgroup calls this together (it holds the tile's barriers; the first
+// one also publishes the tables the caller loaded into twl / down / win).
+// `iq_end` / `out_end`: one past the last sample / record the caller may
+// touch (debug build, bound_check).
+template <int SF, int PREP>
+__device__ __forceinline__ void detect_window(const cf32* iq, unsigned long long base,
+                                              unsigned long long step, unsigned long long iq_end, bool live,
+                                              lphy_detect_rec* out, unsigned long long w,
+                                              unsigned long long out_end, cf32* lds, const cf32* twl,
+                                              const cf32* down, const float* win, ArgMax* red, double* reds,
+                                              float* redn, const Stage<SF>& stg, int slot, int lam, float power_scale,
+                                              unsigned long long* counters) {
+    using G = Geo<SF>;
+    constexpr int N = G::N;
+    constexpr bool DECH = (PREP & kPrepDechirp) != 0, WIN = (PREP & kPrepWindow) != 0;
+    constexpr int WPS = G::LPS > 64 ? G::LPS / 64 : 1;  // waves per window
+    const int tid = threadIdx.x;
+    cf32 raw[16];
+#pragma unroll
+    for (int e = 0; e < G::E; ++e) {
+        raw[e] = czero();
+        if (live) {
+            const unsigned long long idx = base + (unsigned long long)(lam + e * G::LPS) * step;
+            bound_check((long long)idx, (long long)iq_end);
+            raw[e] = iq[idx];
+        }
+    }
+    __syncthreads();  // the tables; the previous tile's readers are done with lds
+#pragma unroll
+    for (int e = 0; e < G::E; ++e) {
+        const int i = lam + e * G::LPS;
+        cf32 x = raw[e];
+        if constexpr (DECH) x = cmul_x(x, down[i]);  // e2e_chain_test.cpp:88-93
+        if constexpr (WIN) x = cscale(x, win[i]);    // LoRaDemod.cpp:96-97
+        stg.put(lds, e, x);
+    }
+    __syncthreads();
+    cf32 v[16];
+    fft_tile<SF, false, true>(v, lds, slot, lam, twl);
+    // keep the bins for the interpolation and the in-order walk; the
+    // lane's share of the sum of |X|^2 (the values local_argmax takes)
+    // ... and its least non-zero one (NaN never taken)
+    double sum = 0.0;
+    float least = __builtin_inff();
+#pragma unroll
+    for (int e = 0; e < G::E; ++e) {
+        lds[G::addr(slot, bin_of<SF>(e, lam))] = v[e];
+        const cf32 sq = v[e] * v[e];
+        const float m2 = sq.x + sq.y;
+        sum += (double)m2;
+        least = (m2 > 0.0f && m2 < least) ? m2 : least;
+    }
+#pragma unroll
+    for (int off = (G::LPS < 64 ? G::LPS : 64) / 2; off >= 1; off >>= 1) {
+        sum += __shfl_xor(sum, off, 64);
+        least = fminf(least, __shfl_xor(least, off, 64));
+    }
+    if constexpr (WPS > 1) {
+        // (visible behind symbol_argmax's first barrier, reused behind
+        // the next tile's)
+        if ((tid & 63) == 0) {
+            reds[tid >> 6] = sum;
+            redn[tid >> 6] = least;
+        }
+    }
+    const ArgMax best = symbol_argmax<SF>(local_argmax<SF>(v, lam), red);
+    if constexpr (WPS > 1) {
+        const int fw = ((tid >> 6) / WPS) * WPS;
+        sum = reds[fw];
+        least = redn[fw];
+#pragma unroll
+        for (int k = 1; k < WPS; ++k) {
+            sum += reds[fw + k];
+            least = fminf(least, redn[fw + k]);
+        }
+    }
+    __syncthreads();  // every bin of the slot written
+    if (lam == 0 && live) {
+        const UnitResult r = unit_result<SF>(lds, slot, best);
+        const float mv = best.v > 0.0f ? best.v : 0.0f;
+        const double c = (double)N * 0x1p-50;
+        const float lo = (float)(sum * (1.0 - c) - (double)mv);
+        const float hi = (float)(sum * (1.0 + c) - (double)mv);
+        // 2^52 ulp(least): ulp = 2^(e - 150) for the biased exponent e (1
+        // for a denormal); a double's exponent field directly
+        const int le = (int)(__float_as_uint(least) >> 23);
+        const double lim = __longlong_as_double((long long)((le ? le : 1) - 98 + 1023) << 52);
+        float rest = lo;
+        if (sum < __builtin_inf() && least < __builtin_inff() && sum <= lim) {
+            rest = (float)(sum - (double)mv);  // S is the reference's total
+        } else if (!(sum < __builtin_inf() && __float_as_uint(lo) == __float_as_uint(hi))) {
+            rest = detect_walk<SF>(lds, slot);
+            atomicAdd(&counters[kCtrDetectSerial], 1ull);
+        }
+        lphy_detect_rec o;
+        o.power = detector_power(mv, power_scale);
+        o.power_avg = detector_power(rest, power_scale);  // 20 log10f(sqrtf(.)) - scale
+        o.findex = r.findex;
+        o.index = (uint16_t)r.idx;
+        o.reserved = 0;
+        bound_check((long long)w, (long long)out_end);
+        out[w] = o;
+    }
+}
+
 // Two waves per SIMD up to SF 10, one above (as k_rg_demod).
 template <int SF, int PREP>
 __global__ __launch_bounds__(kTile, SF <= 10 ? 2 : 1) void k_detect(DetectArgs D) {
@@ -68,7 +183,6 @@ __global__ __launch_bounds__(kTile, SF <= 10 ? 2 : 1) void k_detect(DetectArgs D
     constexpr int N = G::N, T = G::T;
     constexpr bool DECH = (PREP & kPrepDechirp) != 0, WIN = (PREP & kPrepWindow) != 0;
     constexpr bool TAB = N <= 1024;  // chirp + window tables in LDS
-    constexpr int WPS = G::LPS > 64 ? G::LPS / 64 : 1;  // waves per window
     __shared__ cf32 lds[T * G::SSTRIDE];
     __shared__ cf32 twl[N];
     __shared__ cf32 dnl[TAB && DECH ? N : 1];
@@ -93,92 +207,69 @@ __global__ __launch_bounds__(kTile, SF <= 10 ? 2 : 1) void k_detect(DetectArgs D
         const unsigned long long w = t0 + (unsigned)slot;
         const bool live = w < D.windows;
         const unsigned long long base = D.first + (live ? w : 0) * D.hop;
-        cf32 raw[16];
-#pragma unroll
-        for (int e = 0; e < G::E; ++e) {
-            raw[e] = czero();
-            if (live) {
-                const unsigned long long idx = base + (unsigned long long)(lam + e * G::LPS) * D.step;
-                bound_check((long long)idx, (long long)D.total_samples);
-                raw[e] = D.iq[idx];
-            }
+        detect_window<SF, PREP>(D.iq, base, D.step, D.total_samples, live, D.out, w, D.windows, lds, twl, down, win,
+                                red, reds, redn, stg, slot, lam, D.power_scale, D.counters);
+    }
+}
+
+// lphy_hip_detect_ragged: the detector on every whole symbol of every frame
+// of a lphy_ragged_desc table.  The work unit is the global symbol index u,
+// as in k_rg_demod: a persistent grid over tiles of T units, the team finds
+// its unit's frame by binary search over unit_offset (unit_frame; from SF 10
+// on wave-uniform values) and symbol s = u - unit_offset of that frame is the
+// window iq[iq_offset + s N osr + phase + i osr], whose record is out[u].
+// The workgroups past the table's last unit leave at once.
+template <int SF, int PREP>
+__global__ __launch_bounds__(kTile, SF <= 10 ? 2 : 1) void k_detect_ragged(DetectRaggedArgs R) {
+    using G = Geo<SF>;
+    constexpr int N = G::N, T = G::T;
+    constexpr bool DECH = (PREP & kPrepDechirp) != 0, WIN = (PREP & kPrepWindow) != 0;
+    constexpr bool TAB = N <= 1024;  // chirp + window tables in LDS
+    __shared__ cf32 lds[T * G::SSTRIDE];
+    __shared__ cf32 twl[N];
+    __shared__ cf32 dnl[TAB && DECH ? N : 1];
+    __shared__ float wnl[TAB && WIN ? N : 1];
+    __shared__ ArgMax red[kTile / 64];
+    __shared__ double reds[kTile / 64];
+    __shared__ float redn[kTile / 64];
+
+    const unsigned nframes = R.frames;
+    const lphy_ragged_desc* __restrict__ desc = R.desc;
+    const unsigned long long units = desc[nframes].unit_offset;
+    if ((unsigned long long)blockIdx.x * T >= units) return;  // uniform
+
+    const DetectArgs& D = R.D;
+    const int tid = threadIdx.x;
+    for (int i = tid; i < N; i += kTile) {
+        twl[i] = D.tw[i];
+        if constexpr (TAB && DECH) dnl[i] = D.down[i];
+        if constexpr (TAB && WIN) wnl[i] = D.win[i];
+    }
+    const cf32* down = TAB && DECH ? dnl : D.down;
+    const float* win = TAB && WIN ? wnl : D.win;
+
+    const unsigned osr = R.osr;
+    const int slot = tid / G::LPS, lam = tid % G::LPS;
+    const Stage<SF> stg(slot, lam);
+    const unsigned long long stride = (unsigned long long)gridDim.x * T;
+    for (unsigned long long t0 = (unsigned long long)blockIdx.x * T; t0 < units; t0 += stride) {
+        unsigned long long u = t0 + (unsigned)slot;
+        if constexpr (G::LPS >= 64) {  // one symbol per wavefront or more: scalar search
+            const unsigned lo32 = __builtin_amdgcn_readfirstlane((unsigned)u);
+            const unsigned hi32 = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
+            u = ((unsigned long long)hi32 << 32) | lo32;
         }
-        __syncthreads();  // the tables; the previous tile's readers are done with lds
-#pragma unroll
-        for (int e = 0; e < G::E; ++e) {
-            const int i = lam + e * G::LPS;
-            cf32 x = raw[e];
-            if constexpr (DECH) x = cmul_x(x, down[i]);  // e2e_chain_test.cpp:88-93
-            if constexpr (WIN) x = cscale(x, win[i]);    // LoRaDemod.cpp:96-97
-            stg.put(lds, e, x);
-        }
-        __syncthreads();
-        cf32 v[16];
-        fft_tile<SF, false, true>(v, lds, slot, lam, twl);
-        // keep the bins for the interpolation and the in-order walk; the
-        // lane's share of the sum of |X|^2 (the values local_argmax takes)
-        // ... and its least non-zero one (NaN never taken)
-        double sum = 0.0;
-        float least = __builtin_inff();
-#pragma unroll
-        for (int e = 0; e < G::E; ++e) {
-            lds[G::addr(slot, bin_of<SF>(e, lam))] = v[e];
-            const cf32 sq = v[e] * v[e];
-            const float m2 = sq.x + sq.y;
-            sum += (double)m2;
-            least = (m2 > 0.0f && m2 < least) ? m2 : least;
-        }
-#pragma unroll
-        for (int off = (G::LPS < 64 ? G::LPS : 64) / 2; off >= 1; off >>= 1) {
-            sum += __shfl_xor(sum, off, 64);
-            least = fminf(least, __shfl_xor(least, off, 64));
-        }
-        if constexpr (WPS > 1) {
-            // (visible behind symbol_argmax's first barrier, reused behind
-            // the next tile's)
-            if ((tid & 63) == 0) {
-                reds[tid >> 6] = sum;
-                redn[tid >> 6] = least;
-            }
-        }
-        const ArgMax best = symbol_argmax<SF>(local_argmax<SF>(v, lam), red);
-        if constexpr (WPS > 1) {
-            const int fw = ((tid >> 6) / WPS) * WPS;
-            sum = reds[fw];
-            least = redn[fw];
-#pragma unroll
-            for (int k = 1; k < WPS; ++k) {
-                sum += reds[fw + k];
-                least = fminf(least, redn[fw + k]);
-            }
-        }
-        __syncthreads();  // every bin of the slot written
-        if (lam == 0 && live) {
-            const UnitResult r = unit_result<SF>(lds, slot, best);
-            const float mv = best.v > 0.0f ? best.v : 0.0f;
-            const double c = (double)N * 0x1p-50;
-            const float lo = (float)(sum * (1.0 - c) - (double)mv);
-            const float hi = (float)(sum * (1.0 + c) - (double)mv);
-            // 2^52 ulp(least): ulp = 2^(e - 150) for the biased exponent e (1
-            // for a denormal); a double's exponent field directly
-            const int le = (int)(__float_as_uint(least) >> 23);
-            const double lim = __longlong_as_double((long long)((le ? le : 1) - 98 + 1023) << 52);
-            float rest = lo;
-            if (sum < __builtin_inf() && least < __builtin_inff() && sum <= lim) {
-                rest = (float)(sum - (double)mv);  // S is the reference's total
-            } else if (!(sum < __builtin_inf() && __float_as_uint(lo) == __float_as_uint(hi))) {
-                rest = detect_walk<SF>(lds, slot);
-                atomicAdd(&D.counters[kCtrDetectSerial], 1ull);
-            }
-            lphy_detect_rec o;
-            o.power = detector_power(mv, D.power_scale);
-            o.power_avg = detector_power(rest, D.power_scale);  // 20 log10f(sqrtf(.)) - scale
-            o.findex = r.findex;
-            o.index = (uint16_t)r.idx;
-            o.reserved = 0;
-            bound_check((long long)w, (long long)D.windows);
-            D.out[w] = o;
-        }
+        bool live = u < units;
+        const lphy_ragged_desc d = desc[live ? unit_frame(desc, nframes, u) : 0u];
+        const unsigned long long s = u - d.unit_offset;
+        // whole symbols of the frame (samples < 2^31 where it counts)
+        const unsigned n = ((unsigned)d.samples >> SF) / osr;
+        // (a table whose prefix is wrong cannot lead outside the frame, and u < units)
+        live = live && d.unit_offset <= u && d.samples < 0x80000000ull && s < n;
+        const unsigned long long fstep = (unsigned long long)N * osr;
+        const unsigned long long base = d.iq_offset + (live ? s : 0) * fstep + R.phase;
+        detect_window<SF, PREP>(D.iq, base, osr, d.iq_offset + n * fstep, live, D.out, u, units, lds, twl, down, win,
+                                red, reds, redn, stg, slot, lam, D.power_scale, D.counters);
     }
 }
 

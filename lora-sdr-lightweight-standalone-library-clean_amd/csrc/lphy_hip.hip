@@ -260,7 +260,7 @@ void ctx_args(const lphy_hip_ctx* c, ARGS& A) {
     A.counters = c->d_counters;
 }
 
-// Most workgroups the persistent grids of k_rg_demod, k_detect and
+// Most workgroups the persistent grids of k_rg_demod, k_detect, k_detect_ragged and
 // k_tx_samples get on this context (0: no cap; test build only,
 // lphy_hip_test_grid_cap).
 unsigned test_grid_cap(const lphy_hip_ctx* c) {
@@ -640,6 +640,49 @@ int lphy_hip_detect_batch(lphy_hip_ctx* c, const float* d_iq, size_t total_sampl
     if (int rc = detect_check(c, d_iq, total_samples, first, hop, step, windows, d_out, flags, &last))
         return rc > 0 ? 0 : rc;
     return detect_impl(c, d_iq, total_samples, first, hop, step, windows, d_out, flags, (hipStream_t)stream);
+}
+
+// ---- the detector on a ragged table (k_detect_ragged, lphy_detect.h) -------
+namespace {
+// The argument checks of both forms, in the header's order (before any device
+// call): 0 to go on, 1 when there is nothing to do, or the error.
+int detect_ragged_check(const lphy_hip_ctx* c, const void* iq, const void* desc, size_t frames, unsigned phase,
+                        const void* out, unsigned flags) {
+    if (!c) return -EINVAL;
+    if (frames == 0) return 1;
+    if (!iq || !desc || !out) return -EINVAL;
+    if (flags & ~(unsigned)LPHY_DET_DECHIRP) return -EINVAL;
+    if (phase >= c->osr) return -EINVAL;
+    if (frames > 0x7fffffffULL) return -ERANGE;
+    if (c->sf < 7) return -ENOTSUP;
+    return 0;
+}
+
+// units_hint: the call's whole symbols when the caller's table is on the host
+int detect_ragged_impl(lphy_hip_ctx* c, const float* d_iq, const lphy_ragged_desc* d_desc, size_t frames,
+                       unsigned phase, lphy_detect_rec* d_out, unsigned flags, hipStream_t st,
+                       unsigned long long units_hint) {
+    const SfOps* ops = sf_ops(c->sf);
+    if (!ops || !ops->detect_ragged) return -ENOTSUP;  // (an experiment build without this SF's object)
+    HIP_OK(hipSetDevice(c->device));
+    DetectRaggedArgs R{};
+    ctx_args(c, R.D);
+    R.D.iq = reinterpret_cast<const cf32*>(d_iq);
+    R.D.out = d_out;
+    R.D.dechirp = (flags & LPHY_DET_DECHIRP) ? 1 : 0;
+    R.desc = d_desc;
+    R.frames = (unsigned)frames;
+    R.osr = (unsigned)c->osr;
+    R.phase = phase;
+    R.units_hint = units_hint;
+    return ops->detect_ragged(R, st, test_grid_cap(c));
+}
+}  // namespace
+
+int lphy_hip_detect_ragged(lphy_hip_ctx* c, const float* d_iq, const lphy_ragged_desc* d_desc, size_t frames,
+                           unsigned phase, lphy_detect_rec* d_out, unsigned flags, void* stream) {
+    if (int rc = detect_ragged_check(c, d_iq, d_desc, frames, phase, d_out, flags)) return rc > 0 ? 0 : rc;
+    return detect_ragged_impl(c, d_iq, d_desc, frames, phase, d_out, flags, (hipStream_t)stream, 0);
 }
 
 int lphy_hip_detect_serial_count(lphy_hip_ctx* c, unsigned long long* out, int reset) {
@@ -1095,7 +1138,7 @@ int lphy_hip_test_pinned_max(lphy_hip_ctx* c, size_t bytes) {
 }
 
 // Test build only: at most `blocks` workgroups in the persistent grids of
-// k_rg_demod, k_detect and k_tx_samples on this context, after the launchers'
+// k_rg_demod, k_detect, k_detect_ragged and k_tx_samples on this context, after the launchers'
 // own caps (0: the default).  A small call then walks its grid-stride loops
 // more than once, which otherwise needs more tiles than the device holds
 // workgroups.

@@ -28,7 +28,7 @@ int ensure_host_stage(lphy_hip_ctx* c, size_t bytes) {
 //
 // kMirror: demod, decode and modulate (the per-packet calls of the lora_phy::
 // API) go through the pinned mirror when their copied slices fit
-// it, one DMA copy each way; the other seven copy slice by slice from and to
+// it, one DMA copy each way; the other eight copy slice by slice from and to
 // the caller's memory.  Which call does which is a measured choice, not an
 // accident of this code.
 enum HostCopy { kPageable, kMirror };
@@ -176,6 +176,21 @@ int lphy_hip_detect_host(lphy_hip_ctx* c, const float* h_iq, size_t total_sample
     if (int rc = hc.begin(detect_plan(span, windows), {h_iq + 2 * first, h_out})) return rc;
     return hc.finish(detect_impl(c, hc.dev<float>(0), span, 0, hop, step, windows, hc.dev<lphy_detect_rec>(1), flags,
                                  hc.stream()));
+}
+
+// The ragged detector on host buffers: the table is checked first, then the
+// descriptors' IQ extent and the frames + 1 records in, one launch sized by
+// the table's whole symbols, that many records out.
+int lphy_hip_detect_ragged_host(lphy_hip_ctx* c, const float* h_iq, const lphy_ragged_desc* h_desc, size_t frames,
+                                unsigned phase, lphy_detect_rec* h_out, unsigned flags) {
+    if (int rc = detect_ragged_check(c, h_iq, h_desc, frames, phase, h_out, flags)) return rc > 0 ? 0 : rc;
+    uint64_t iq_samples = 0, units = 0;
+    if (int rc = detect_ragged_extent((uint64_t)c->N * c->osr, h_desc, frames, &iq_samples, &units)) return rc;
+    if (units == 0) return 0;  // no frame holds a whole symbol: nothing is written
+    HostCall hc(c, kPageable);
+    if (int rc = hc.begin(detect_ragged_plan(iq_samples, frames, units), {h_iq, h_desc, h_out})) return rc;
+    return hc.finish(detect_ragged_impl(c, hc.dev<float>(0), hc.dev<lphy_ragged_desc>(1), frames, phase,
+                                        hc.dev<lphy_detect_rec>(2), flags, hc.stream(), units));
 }
 
 int lphy_hip_decode_host(lphy_hip_ctx* c, const uint16_t* h_syms, size_t count,

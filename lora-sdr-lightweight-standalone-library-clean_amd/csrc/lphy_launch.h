@@ -259,6 +259,40 @@ int launch_detect_sf(const DetectArgs& D, hipStream_t st, unsigned grid_cap) {
     }
 }
 
+// lphy_hip_detect_ragged (lphy_detect.h), SF 7-12: one persistent launch over
+// tiles of Geo<SF>::T whole symbols.  The grid covers the call's units when
+// the host knows them (units_hint), else the resident grid launches and the
+// workgroups past the last unit leave at once (grid_cap as in
+// launch_ragged_sf).
+template <int SF>
+int launch_detect_ragged_sf(const DetectRaggedArgs& R, hipStream_t st, unsigned grid_cap) {
+    if constexpr (SF < 7) {
+        (void)R; (void)st; (void)grid_cap;
+        return -ENOTSUP;
+    } else {
+        auto go = [&](auto p) {
+            constexpr int PREP = decltype(p)::value;
+            constexpr int T = Geo<SF>::T;
+            unsigned long long grid = (unsigned long long)resident_grid<&k_detect_ragged<SF, PREP>>();
+            if (R.units_hint) {
+                const unsigned long long tiles = (R.units_hint + T - 1) / T;
+                if (grid > tiles) grid = tiles;
+            }
+            if (grid_cap && grid > grid_cap) grid = grid_cap;
+            hipLaunchKernelGGL((k_detect_ragged<SF, PREP>), dim3((unsigned)grid), dim3(kTile), 0, st, R);
+        };
+        const int prep = (R.D.dechirp ? kPrepDechirp : 0) | (R.D.win ? kPrepWindow : 0);
+        switch (prep) {
+            case 0: go(std::integral_constant<int, 0>{}); break;
+            case kPrepDechirp: go(std::integral_constant<int, kPrepDechirp>{}); break;
+            case kPrepWindow: go(std::integral_constant<int, kPrepWindow>{}); break;
+            default: go(std::integral_constant<int, kPrepDechirp | kPrepWindow>{}); break;
+        }
+        HIP_OK(hipGetLastError());
+        return 0;
+    }
+}
+
 template <int SF>
 int launch_estimate_sf(const DemodArgs& A, hipStream_t st) {
     const int fpt = A.est_units <= Geo<SF>::T ? Geo<SF>::T / A.est_units : 1;

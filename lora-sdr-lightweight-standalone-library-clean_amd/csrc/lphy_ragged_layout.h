@@ -85,6 +85,28 @@ inline int estimate_ragged_extent(const lphy_ragged_desc* h_desc, size_t frames,
     return 0;
 }
 
+// A caller's table for lphy_hip_detect_ragged_host: ragged_extent's limits
+// and prefix check on the three fields that call reads (iq_offset, samples,
+// unit_offset; step = N * osr), the extent of the IQ they name and the whole
+// symbols, one record each.  sym_offset is not read.
+inline int detect_ragged_extent(uint64_t step, const lphy_ragged_desc* h_desc, size_t frames, uint64_t* iq_samples,
+                                uint64_t* units) {
+    uint64_t iq = 0, unit = 0;
+    for (size_t f = 0; f < frames; ++f) {
+        const lphy_ragged_desc& d = h_desc[f];
+        if (d.samples >= kRaggedMaxSamples) return -ERANGE;
+        if (d.unit_offset != unit) return -EINVAL;
+        if (d.iq_offset > (uint64_t(1) << 48)) return -ERANGE;
+        unit += d.samples / step;
+        if (unit >= kRaggedMaxUnits) return -ERANGE;
+        if (d.iq_offset + d.samples > iq) iq = d.iq_offset + d.samples;
+    }
+    if (h_desc[frames].unit_offset != unit) return -EINVAL;
+    *iq_samples = iq;
+    *units = unit;
+    return 0;
+}
+
 // lphy_hip_tx_layout: the table of frames that carry h_len_bytes[f] payload
 // bytes each, (2 len + 2) symbols of `step` samples, as ragged_layout packs
 // them in mode 1 - so sym_offset / 2 is the exclusive prefix of len and the

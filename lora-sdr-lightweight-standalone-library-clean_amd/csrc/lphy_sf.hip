@@ -20,6 +20,7 @@ template int launch_estimate_sf<LPHY_SF>(const DemodArgs&, hipStream_t);
 template int launch_ragged_sf<LPHY_SF>(const RaggedArgs&, hipStream_t, unsigned);
 template int launch_detect_sf<LPHY_SF>(const DetectArgs&, hipStream_t, unsigned);
 template int launch_estimate_ragged_sf<LPHY_SF>(const RaggedArgs&, unsigned long long, hipStream_t);
+template int launch_detect_ragged_sf<LPHY_SF>(const DetectRaggedArgs&, hipStream_t, unsigned);
 }  // namespace
 
 #ifdef LPHY_DEBUG_BOUNDS
@@ -54,6 +55,7 @@ const SfOps LPHY_CAT(sf_ops_, LPHY_SF) = {
     &launch_ragged_sf<LPHY_SF>,
     &launch_detect_sf<LPHY_SF>,
     &launch_estimate_ragged_sf<LPHY_SF>,
+    &launch_detect_ragged_sf<LPHY_SF>,
 };
 }  // namespace lphy
 #endif

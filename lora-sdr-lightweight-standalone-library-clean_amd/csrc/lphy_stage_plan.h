@@ -61,7 +61,7 @@ struct StagePlan {
 constexpr size_t kIqBytes = 2 * sizeof(float);  // one complex sample
 constexpr size_t kMetaBytes = sizeof(lphy_frame_meta);
 
-// The plans of the ten *_host entry points, slices in the order named.
+// The plans of the eleven *_host entry points, slices in the order named.
 
 // iq | syms | bytes | meta | spec (the SF 11-12 speculation records); `per`:
 // lphy_hip_syms_per_frame
@@ -140,12 +140,24 @@ inline StagePlan estimate_ragged_plan(size_t iq_samples, size_t frames) {
         .add(frames * kMetaBytes, kStageInOut);
 }
 
+// iq | desc (frames + 1 records) | records, one per whole symbol
+// (lphy_hip_detect_ragged_host).  With a checked table every record has
+// exactly one owner, so the records only come back.
+inline StagePlan detect_ragged_plan(size_t iq_samples, size_t frames, size_t units) {
+    return StagePlan()
+        .add(iq_samples * kIqBytes, kStageIn)
+        .add((frames + 1) * sizeof(lphy_ragged_desc), kStageIn)
+        .add(units * sizeof(lphy_detect_rec), kStageOut);
+}
+
 // Staging every *_host entry point needs for calls of up to `frames` frames
 // of `frame_samples` samples, or one buffer of frames * frame_samples: the
-// largest of the ten plans at that shape (the ragged estimate's slices are
+// largest of the eleven plans at that shape (the ragged estimate's slices are
 // among the ragged demodulator's, so it never sets the size).  Demodulation in modes 1/2, which
 // give no fewer symbols than mode 0; ragged frames of frame_samples each; one
-// detector window per N samples of the buffer; all the frames' symbols in one
+// detector window per N samples of the buffer; one ragged detector record per
+// whole symbol of the buffer (16 B a symbol: more than the ragged
+// demodulator's outputs); all the frames' symbols in one
 // decode; ragged transmit frames of frame_samples each, gaps or not (the
 // ragged plan's slices less the records, so it never sets the size); one frame's symbols in one modulate (mod_scratch: its
 // mod_scratch_bytes).  A call past that grows the staging.
@@ -155,6 +167,7 @@ inline size_t host_stage_bytes(size_t N, size_t osr, size_t frames, size_t frame
     return std::max({demod_plan(frames, frame_samples, per).end,
                      ragged_plan(n, frames, frames * ((per + 1) & ~size_t(1))).end,
                      detect_plan(n, n / N).end,
+                     detect_ragged_plan(n, frames, n / step).end,
                      decode_plan(frames * (total + 2)).end,
                      estimate_plan(n).end,
                      estimate_ragged_plan(n, frames).end,

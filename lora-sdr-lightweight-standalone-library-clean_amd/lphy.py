@@ -111,6 +111,7 @@ EXPORTS = (
     "lphy_hip_compensate_batch", "lphy_hip_compensate_ragged", "lphy_hip_compensate_batch_host",
     "lphy_hip_modulate_ragged", "lphy_hip_tx_ragged", "lphy_hip_tx_ragged_host", "lphy_hip_tx_layout",
     "lphy_hip_estimate_ragged", "lphy_hip_estimate_ragged_host",
+    "lphy_hip_detect_ragged", "lphy_hip_detect_ragged_host",
 )
 
 WHITEN_SX1232, WHITEN_SX1272, WHITEN_SX1272_LFSR = 0, 1, 2
@@ -170,6 +171,8 @@ def load(path: Path | None = None) -> C.CDLL:
     L.lphy_hip_detect_batch.argtypes = [_vp, _vp, _sz, _sz, _sz, _sz, _sz, _vp, C.c_uint, _vp]
     L.lphy_hip_detect_host.argtypes = [_vp, _vp, _sz, _sz, _sz, _sz, _sz, _vp, C.c_uint]
     L.lphy_hip_detect_serial_count.argtypes = [_vp, C.POINTER(C.c_ulonglong), C.c_int]
+    L.lphy_hip_detect_ragged.argtypes = [_vp, _vp, _vp, _sz, C.c_uint, _vp, C.c_uint, _vp]
+    L.lphy_hip_detect_ragged_host.argtypes = [_vp, _vp, _vp, _sz, C.c_uint, _vp, C.c_uint]
     L.lphy_hip_decode_batch.argtypes = [_vp, _vp, _sz, _sz, _vp, _vp, _vp]
     L.lphy_hip_estimate_batch.argtypes = [_vp, _vp, _sz, _sz, _sz, _vp, _vp]
     L.lphy_hip_estimate_ragged.argtypes = [_vp, _vp, _vp, _sz, _sz, _vp, _vp]
@@ -372,6 +375,48 @@ class Demodulator:
         _chk(self.lib.lphy_hip_detect_host(self.ctx, iq.ctypes.data, iq.size, first, hop, step, windows,
                                            (out if windows else pad).ctypes.data, flags), "lphy_hip_detect_host")
         return out
+
+    def detect_ragged(self, iq, desc, frames, out, phase=0, flags=0, stream=None, iq_samples=None, units=None):
+        """LoRaDetector::detect on every whole symbol of every frame of a
+        ragged table in one launch: symbol s of frame f reads
+        iq[desc[f]["iq_offset"] + s*N*osr + phase + i*osr], i < N, prepared as
+        detect_batch prepares a window, and its record goes to
+        out[desc[f]["unit_offset"] + s] (lphy_hip_detect_ragged).  `desc`:
+        device tensor of frames + 1 RAGGED_DESC_DTYPE records; `out`: device
+        tensor of desc[frames]["unit_offset"] DETECT_DTYPE records.
+        iq_samples / units: the extents the descriptors span (checked against
+        the tensors).  Asynchronous."""
+        dv = self.device
+        p_iq = _dev_buf(iq, "iq", dv, (iq_samples or 0) * 8, None)
+        p_desc = _dev_buf(desc, "desc", dv, (frames + 1) * 32, None)
+        p_out = _dev_buf(out, "out", dv, (units or 0) * 16, None)
+        _chk(self.lib.lphy_hip_detect_ragged(self.ctx, p_iq, p_desc, frames, phase, p_out, flags, stream),
+             "lphy_hip_detect_ragged")
+
+    def detect_ragged_host(self, iq_flat: np.ndarray, lengths_or_desc, phase: int = 0, flags: int = 0):
+        """The same on host samples.  `lengths_or_desc` is a list of sample
+        counts (frames packed back to back in `iq_flat`) or a
+        RAGGED_DESC_DTYPE array of frames + 1 records (iq_offset, samples and
+        unit_offset are read).  Returns (records, desc): one DETECT_DTYPE
+        record per whole symbol, frame f's first at desc["unit_offset"][f]."""
+        a = np.asarray(lengths_or_desc)
+        desc = (np.ascontiguousarray(a) if a.dtype == RAGGED_DESC_DTYPE
+                else self.ragged_layout(a, MODE_DEMODULATE))
+        frames = desc.size - 1
+        iq = np.ascontiguousarray(iq_flat, np.complex64).reshape(-1)
+        d = desc[:-1]
+        n_iq = int((d["iq_offset"] + d["samples"]).max()) if d.size else 0
+        if iq.size < n_iq:
+            raise ValueError(f"iq: {iq.size} samples, the descriptors span {n_iq}")
+        units = int(desc["unit_offset"][-1])
+        out = np.zeros(units, DETECT_DTYPE)
+        pad = np.zeros(1, np.complex64)
+        opad = np.zeros(1, DETECT_DTYPE)
+        _chk(self.lib.lphy_hip_detect_ragged_host(self.ctx, (iq if iq.size else pad).ctypes.data,
+                                                  desc.ctypes.data, frames, phase,
+                                                  (out if units else opad).ctypes.data, flags),
+             "lphy_hip_detect_ragged_host")
+        return out, desc
 
     def detect_serial_count(self, reset: bool = True) -> int:
         """Windows whose power_avg took the in-order walk of the bins because
