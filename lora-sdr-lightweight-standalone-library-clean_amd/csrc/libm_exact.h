@@ -23,7 +23,13 @@
 // sincosf tables were additionally read back from this image's libm.so.6
 // .rodata.  tests/cpp/libm_exact_check.cpp compares every function against
 // the host glibc over all 2^32 float inputs (sincosf) or >10^8 inputs
-// (atan2f); see DESIGN.md §"Transcendentals".
+// (atan2f), as g++ compiles this text for the host.  What hipcc makes of it
+// for the device (inv_pio4_shift, the AMDGPU division, square roots,
+// conversions and subnormals) is compared with glibc by
+// tests/test_gpu_libm.py through the test build's probe lphy_hip_test_libm
+// (lphy_testing.h), over the bit-pattern sets of tests/libm_cases.py, which
+// enter every branch below from both sides of its threshold; see DESIGN.md
+// §"Transcendentals".
 //
 // Everything here must be compiled with -ffp-contract=off: the only fused
 // operations are the explicit fma() calls.

@@ -1152,6 +1152,82 @@ int lphy_hip_test_counter(lphy_hip_ctx* c, int idx, unsigned long long* out, int
     if (idx < 0 || idx >= kCounters) return -EINVAL;
     return read_counters(c, idx, 1, out, reset);
 }
+
+namespace {
+extern "C++" {
+// One element per input, grid-stride; each op calls what the kernels call,
+// the way they call it (SPLIT: rotate_sample's choice; SQRTF: unit_result's
+// sqrtf; DETECTOR_POWER: lphy_demod.h's function itself).
+template <int OP>
+__global__ __launch_bounds__(kTile) void k_test_libm(const float* a, const float* b, float* out0, float* out1,
+                                                     unsigned long long n) {
+    const unsigned long long stride = (unsigned long long)gridDim.x * kTile;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * kTile + threadIdx.x; i < n; i += stride) {
+        const float x = a[i];
+        if constexpr (OP == LPHY_LIBM_SINCOS_EXACT || OP == LPHY_LIBM_SINCOS_SPLIT || OP == LPHY_LIBM_SINCOS_LARGE) {
+            float sn, cs;
+            if constexpr (OP == LPHY_LIBM_SINCOS_EXACT) {
+                lphy_libm::sincosf_exact(x, &sn, &cs);
+            } else if constexpr (OP == LPHY_LIBM_SINCOS_SPLIT) {
+                const bool large = lphy_libm::sincosf_needs_large(x);
+                if (large) lphy_libm::sincosf_large(x, &sn, &cs);
+                else lphy_libm::sincosf_fast(x, &sn, &cs);
+            } else {
+                lphy_libm::sincosf_large(x, &sn, &cs);
+            }
+            out0[i] = sn;
+            out1[i] = cs;
+        } else if constexpr (OP == LPHY_LIBM_ATAN2) {
+            out0[i] = lphy_libm::atan2f_exact(x, b[i]);
+        } else if constexpr (OP == LPHY_LIBM_CABS) {
+            out0[i] = lphy_libm::cabsf_exact(x, b[i]);
+        } else if constexpr (OP == LPHY_LIBM_LOGF) {
+            out0[i] = lphy_libm::logf_exact(x);
+        } else if constexpr (OP == LPHY_LIBM_LOG10F) {
+            out0[i] = lphy_libm::log10f_exact(x);
+        } else if constexpr (OP == LPHY_LIBM_SQRTF) {
+            out0[i] = sqrtf(x);
+        } else {
+            out0[i] = detector_power(x, b[i]);
+        }
+    }
+}
+}  // extern "C++"
+}  // namespace
+
+// Test build only (csrc/lphy_testing.h): libm_exact.h, the device sqrtf and
+// detector_power over the caller's inputs, as this translation unit's flags
+// compile them for the device.
+int lphy_hip_test_libm(lphy_hip_ctx* c, int op, const float* d_a, const float* d_b, float* d_out0, float* d_out1,
+                       size_t n, void* stream) {
+    if (!c || !d_a || !d_out0 || op < 0 || op >= LPHY_LIBM_OPS) return -EINVAL;
+    const bool two_in = op == LPHY_LIBM_ATAN2 || op == LPHY_LIBM_CABS || op == LPHY_LIBM_DETECTOR_POWER;
+    const bool two_out = op <= LPHY_LIBM_SINCOS_LARGE;
+    if ((two_in && !d_b) || (two_out && !d_out1)) return -EINVAL;
+    if (n == 0) return 0;
+    if ((unsigned long long)n >= (1ull << 32)) return -ERANGE;
+    HIP_OK(hipSetDevice(c->device));
+    const unsigned long long blocks = ((unsigned long long)n + kTile - 1) / kTile;
+    const dim3 grid((unsigned)(blocks < 2048 ? blocks : 2048)), block(kTile);
+    const hipStream_t st = (hipStream_t)stream;
+    const unsigned long long count = n;
+    switch (op) {
+#define LPHY_LIBM_CASE(OP) \
+    case OP: hipLaunchKernelGGL(k_test_libm<OP>, grid, block, 0, st, d_a, d_b, d_out0, d_out1, count); break
+        LPHY_LIBM_CASE(LPHY_LIBM_SINCOS_EXACT);
+        LPHY_LIBM_CASE(LPHY_LIBM_SINCOS_SPLIT);
+        LPHY_LIBM_CASE(LPHY_LIBM_SINCOS_LARGE);
+        LPHY_LIBM_CASE(LPHY_LIBM_ATAN2);
+        LPHY_LIBM_CASE(LPHY_LIBM_CABS);
+        LPHY_LIBM_CASE(LPHY_LIBM_LOGF);
+        LPHY_LIBM_CASE(LPHY_LIBM_LOG10F);
+        LPHY_LIBM_CASE(LPHY_LIBM_SQRTF);
+        LPHY_LIBM_CASE(LPHY_LIBM_DETECTOR_POWER);
+#undef LPHY_LIBM_CASE
+    }
+    HIP_OK(hipGetLastError());
+    return 0;
+}
 #endif
 
 int lphy_hip_bounds_violations(lphy_hip_ctx* c, unsigned long long* out, int reset) {

@@ -20,9 +20,42 @@
 //     launchers: no kernel reads it, and the product library has neither the
 //     symbol nor the cap.  The uniform kernels (k_wave, k_demod, k_frames)
 //     are outside it: the suite's larger batches walk their grids many times.
+//   * lphy_hip_test_libm(ctx, op, d_a, d_b, d_out0, d_out1, n, stream): the
+//     functions of libm_exact.h, the device sqrtf and detector_power as the
+//     kernels call them, one element per input, so that the tests see what
+//     hipcc makes of the header for the device over inputs they choose
+//     (tests/test_gpu_libm.py against glibc through the oracle).  The product
+//     library has no such symbol.
 #pragma once
 
+#include <cstddef>
 #include <cstdlib>
+
+// lphy_hip_test_libm's `op`: a is the argument (ATAN2: y, CABS: re,
+// DETECTOR_POWER: max_value), b the second one where there is one (ATAN2: x,
+// CABS: im, DETECTOR_POWER: power_scale); the sincos ops write sin to out0
+// and cos to out1, the others their value to out0.
+enum lphy_test_libm_op {
+    LPHY_LIBM_SINCOS_EXACT = 0,    // sincosf_exact
+    LPHY_LIBM_SINCOS_SPLIT = 1,    // sincosf_needs_large ? sincosf_large : sincosf_fast (rotate_sample)
+    LPHY_LIBM_SINCOS_LARGE = 2,    // sincosf_large alone, whatever the argument
+    LPHY_LIBM_ATAN2 = 3,
+    LPHY_LIBM_CABS = 4,
+    LPHY_LIBM_LOGF = 5,
+    LPHY_LIBM_LOG10F = 6,
+    LPHY_LIBM_SQRTF = 7,           // the device sqrtf of unit_result
+    LPHY_LIBM_DETECTOR_POWER = 8,  // detector_power (lphy_demod.h)
+    LPHY_LIBM_OPS = 9,
+};
+
+#ifdef LPHY_TEST_PATHS
+struct lphy_hip_ctx;
+// Test build only.  -EINVAL for a null ctx, a null pointer the op uses (d_b
+// and d_out1 may be null for the ops that do not) or an unknown op; then 0
+// for n == 0; -ERANGE for n >= 2^32.  Asynchronous on `stream`.
+extern "C" int lphy_hip_test_libm(lphy_hip_ctx* ctx, int op, const float* d_a, const float* d_b, float* d_out0,
+                                  float* d_out1, size_t n, void* stream);
+#endif
 
 // A context's device counters (lphy_hip_ctx::d_counters, kCounters slots),
 // each with a slot of its own (the modulator's fallback count

@@ -46,6 +46,9 @@ F_EXACT_ROTATION = 64  # every symbol with the reference's per-sample rotation
 F_SCAN_FIRST = 256  # modes 1/2: whole-frame max-abs pre-scan (no speculation)
 F_DEBUG_RECHECK = 512  # every symbol / estimated frame left to the exact re-run
 F_FRAMES_KERNEL = 1024  # SF 7-10: k_frames where k_wave would run (test build; the certificate tests on k_frames)
+# lphy_hip_test_libm's ops (test build; csrc/lphy_testing.h lphy_test_libm_op)
+(LIBM_SINCOS_EXACT, LIBM_SINCOS_SPLIT, LIBM_SINCOS_LARGE, LIBM_ATAN2, LIBM_CABS, LIBM_LOGF, LIBM_LOG10F,
+ LIBM_SQRTF, LIBM_DETECTOR_POWER) = range(9)
 WINDOW_NONE = 0
 WINDOW_HANN = 1
 # Smallest batch new Demodulators send to the fused kernels
@@ -738,6 +741,24 @@ class Demodulator:
         fn = self.lib.lphy_hip_test_grid_cap
         fn.argtypes = [_vp, C.c_uint]
         _chk(fn(self.ctx, int(blocks)), "lphy_hip_test_grid_cap")
+
+    def libm_probe(self, op: int, a, b=None, stream=None):
+        """Test build only: csrc/libm_exact.h, the device sqrtf and
+        detector_power as compiled for the device, on float32 device tensors
+        (op: LIBM_*; b: the second argument of LIBM_ATAN2 / LIBM_CABS /
+        LIBM_DETECTOR_POWER) -> (out0, out1) device tensors, out1 (the
+        cosine) None for the ops with one result.  Asynchronous."""
+        import torch
+        fn = self.lib.lphy_hip_test_libm
+        fn.argtypes = [_vp, C.c_int, _vp, _vp, _vp, _vp, _sz, _vp]
+        n, dv = a.numel(), self.device
+        p_a = _dev_buf(a, "a", dv, n * 4, 4)
+        p_b = None if b is None else _dev_buf(b, "b", dv, n * 4, 4)
+        out0 = torch.empty_like(a)
+        out1 = torch.empty_like(a) if op in (LIBM_SINCOS_EXACT, LIBM_SINCOS_SPLIT, LIBM_SINCOS_LARGE) else None
+        _chk(fn(self.ctx, int(op), p_a, p_b, out0.data_ptr(), None if out1 is None else out1.data_ptr(), n, stream),
+             "lphy_hip_test_libm")
+        return out0, out1
 
     def recheck_count(self, reset: bool = True) -> int:
         """Symbols the fused kernel re-ran with the exact rotation (device sync)."""

@@ -979,3 +979,29 @@ double orc_bench(int mode, unsigned sf, unsigned bw_hz, const float* iq,
     clock_gettime(CLOCK_MONOTONIC, &t1);
     return (double)(t1.tv_sec - t0.tv_sec) + 1e-9 * (double)(t1.tv_nsec - t0.tv_nsec);
 }
+
+/* ---------------------------------------------------------------------- */
+/* glibc's own libm over arrays: the reference of the device's             */
+/* csrc/libm_exact.h (tests/test_gpu_libm.py, tests/test_libm_cases_cpu.py). */
+/* op as lphy_test_libm_op (csrc/lphy_testing.h).  b and out1 may be NULL   */
+/* for the ops that do not use them.  Returns 0, or -EINVAL for another op. */
+/* ---------------------------------------------------------------------- */
+int orc_libm(int op, const float* a, const float* b, float* out0, float* out1, size_t n) {
+    if (op < 0 || op > 8) return -EINVAL;
+    for (size_t i = 0; i < n; ++i) {
+        const float x = a[i];
+        switch (op) {
+            case 0: case 1: case 2: sincosf(x, &out0[i], &out1[i]); break;
+            case 3: out0[i] = atan2f(x, b[i]); break;
+            case 4: out0[i] = cabsf(CMPLXF(x, b[i])); break;
+            case 5: out0[i] = logf(x); break;
+            case 6: out0[i] = log10f(x); break;
+            case 7: out0[i] = sqrtf(x); break;
+            default: { /* LoRaDetector.hpp:64 */
+                const float fundamental = sqrtf(x);
+                out0[i] = 20.0f * log10f(fundamental) - b[i];
+            }
+        }
+    }
+    return 0;
+}

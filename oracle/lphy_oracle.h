@@ -99,6 +99,15 @@ uint32_t orc_lorawan_mic(const uint8_t key[16], int uplink, uint32_t devaddr,
 void orc_lorawan_parse(const uint8_t key[16], const uint8_t* bytes, size_t len,
                        int64_t* rec);
 
+/* glibc's libm over arrays, the reference of csrc/libm_exact.h as compiled
+ * for the device.  op as lphy_test_libm_op (csrc/lphy_testing.h): 0-2
+ * sincosf(a) -> out0 = sin, out1 = cos; 3 atan2f(a, b); 4 cabsf(a + i b);
+ * 5 logf; 6 log10f; 7 sqrtf; 8 20*log10f(sqrtf(a)) - b
+ * (LoRaDetector.hpp:64).  b / out1 may be NULL where unused.  Returns 0 or
+ * -EINVAL for another op. */
+int orc_libm(int op, const float* a, const float* b, float* out0, float* out1,
+             size_t n);
+
 /* Multi-threaded timing harness for bench.py's cpu_baseline ("port" kind):
  * mode 1 = dechirp + lora_demodulate + lora_decode per frame,
  * mode 0 = demodulate + decode.  Returns wall seconds. */

@@ -122,7 +122,21 @@ class Oracle(_LoRaWANMixin):
         L.orc_bench.restype = C.c_double
         self._lw_types(L, "orc_")
         L.orc_lorawan_parse.argtypes = [_u8p, _u8p, C.c_size_t, C.POINTER(C.c_int64)]
+        L.orc_libm.argtypes = [C.c_int, _f32p, _f32p, _f32p, _f32p, C.c_size_t]
 
+    # --- glibc's libm over arrays (the reference of csrc/libm_exact.h) ------
+    def libm(self, op, a, b=None):
+        """glibc's function of lphy_test_libm_op `op` (csrc/lphy_testing.h,
+        tests/libm_cases.py) on float32 arrays -> (out0, out1); out1 (the
+        cosine) is None for the ops with one result."""
+        a = np.ascontiguousarray(a, np.float32)
+        b = None if b is None else np.ascontiguousarray(b, np.float32)
+        assert b is None or b.shape == a.shape
+        out0 = np.empty_like(a)
+        out1 = np.empty_like(a) if op <= 2 else None
+        rc = self.lib.orc_libm(int(op), _p(a, _f32p), _p(b, _f32p), _p(out0, _f32p), _p(out1, _f32p), a.size)
+        assert rc == 0, rc
+        return out0, out1
 
     # --- LoRaCodes.hpp helpers (SURVEY 8f rank 3) -------------------------
     def gray(self, v, to_binary):
@@ -264,6 +278,30 @@ class Oracle(_LoRaWANMixin):
         t = self.lib.orc_bench(mode, sf, bw_hz, _p(x, _f32p), frames, frame_samples,
                                _p(out, _u8p), threads)
         return t, out
+
+
+class HostLibm:
+    """The host build of csrc/libm_exact.h over arrays (tests/cpp/libm_exact_capi.cpp),
+    compiled into `build_dir` with the flags of the other host checks
+    (tests/test_cpu_checks.py)."""
+
+    def __init__(self, build_dir):
+        import subprocess
+        so = Path(build_dir) / "liblibm_exact_capi.so"
+        subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", str(so),
+                        str(ROOT / "tests" / "cpp" / "libm_exact_capi.cpp")], check=True)
+        self.lib = C.CDLL(str(so))
+        self.lib.lphy_libm_host.argtypes = [C.c_int, _f32p, _f32p, _f32p, _f32p, C.c_size_t]
+
+    def libm(self, op, a, b=None):
+        """As Oracle.libm, through the header."""
+        a = np.ascontiguousarray(a, np.float32)
+        b = None if b is None else np.ascontiguousarray(b, np.float32)
+        out0 = np.empty_like(a)
+        out1 = np.empty_like(a) if op <= 2 else None
+        rc = self.lib.lphy_libm_host(int(op), _p(a, _f32p), _p(b, _f32p), _p(out0, _f32p), _p(out1, _f32p), a.size)
+        assert rc == 0, rc
+        return out0, out1
 
 
 class Reference(_LoRaWANMixin):
