@@ -43,6 +43,10 @@
  *   lphy_hip_compensate_ragged own offsets read on the device from its
  *                          lphy_frame_meta (frames of one length / of different
  *                          lengths, lphy_ragged_desc)
+ *   lphy_hip_lorawan_build_ragged lorawan::build_frame src/lorawan/lorawan.cpp:100-136
+ *   lphy_hip_lorawan_parse_ragged lorawan::parse_frame src/lorawan/lorawan.cpp:138-177
+ *                          for frames of different lengths on that table, the
+ *                          key found by DevAddr (lphy_lorawan_session)
  *
  * Batch layout in HBM:
  *   IQ      interleaved float32 (I,Q) = std::complex<float>, frame f at
@@ -769,6 +773,132 @@ int lphy_hip_lorawan_parse_batch(const uint8_t* d_bytes, size_t frames, size_t s
  * serialised process-wide.  Returns 0, -EINVAL, -ENODEV or -EIO. */
 int lphy_hip_lorawan_mic_host(int device, const uint8_t key[16], int uplink, uint32_t devaddr, uint32_t fcnt,
                               const uint8_t* data, size_t len, uint32_t* mic);
+
+/* ------------------------------------------------------------------------
+ * LoRaWAN on the ragged table: lorawan::build_frame (lorawan.cpp:100-136) and
+ * parse_frame's checks (lorawan.cpp:138-177) for frames of different lengths,
+ * on the lphy_ragged_desc table of the ragged PHY calls.  Both directions are
+ * then a chain of launches on one stream with no host read of the table:
+ *   receive   lphy_hip_estimate_ragged -> lphy_hip_compensate_ragged ->
+ *             lphy_hip_demod_ragged(LPHY_F_DECODE) -> lphy_hip_lorawan_parse_ragged
+ *   transmit  lphy_hip_lorawan_build_ragged -> lphy_hip_tx_ragged
+ * Neither call takes a context: symbol_samples is N * osr of the context whose
+ * calls share the table (lphy_hip_symbol_samples).  Keys as above: 16-byte
+ * records at d_keys, 16-byte aligned.  Both calls are one launch, asynchronous
+ * on `stream`, allocate nothing on the device and read nothing of the table on
+ * the host; one thread takes one frame.  Of a descriptor only samples and
+ * sym_offset are read (not iq_offset, not unit_offset, not record [frames]).
+ * --------------------------------------------------------------------- */
+
+/* N * osr of the context: the samples of one symbol.  0 for a null ctx. */
+size_t lphy_hip_symbol_samples(const lphy_hip_ctx* ctx);
+
+typedef struct lphy_lorawan_tx {   /* 32 bytes, one frame to build */
+    uint64_t src_offset;   /* FOpts, then FRMPayload, at d_src + src_offset   */
+    uint32_t devaddr;
+    uint32_t key;          /* index into d_keys                               */
+    uint32_t payload_len;  /* FRMPayload bytes                                */
+    uint16_t fcnt;
+    uint8_t  mtype;        /* MHDR = mtype << 5 | (major & 3)                 */
+    uint8_t  major;
+    uint8_t  fctrl;        /* FCtrl = (fctrl & 0xF0) | fopts_len              */
+    uint8_t  fopts_len;    /* 0..15                                           */
+    uint8_t  reserved[6];
+} lphy_lorawan_tx;
+
+/* build_frame for every frame of a table.  Frame f, with t = d_tx[f] and d =
+ * d_desc[f], has L = 12 + t.fopts_len + t.payload_len bytes and a slot of cap
+ * = (d.samples / symbol_samples - 2) / 2 bytes (0 when the frame has fewer
+ * than two symbols): what lphy_hip_tx_ragged sends for it and the receiver
+ * parses.
+ *   - Success: the bytes MHDR | DevAddr (LE) | FCtrl | FCnt (LE) | FOpts |
+ *     FRMPayload | MIC (LE) go to d_bytes + d.sym_offset / 2, bit for bit what
+ *     build_frame leaves in tmp_bytes: uplink = (t.mtype & 1) == 0, fcnt
+ *     widened to 32 bits for B0, the key d_keys[t.key].  With d_syms_out, the
+ *     2L symbols lora_encode gives for them (build_frame's output) go to
+ *     d_syms_out + d.sym_offset.  d_status[f] = 2L, build_frame's return.
+ *   - A failure writes d_status[f] and nothing else.  In this order: -EINVAL
+ *     for t.fopts_len > 15 or t.mtype > 7; -ENOKEY for t.key >= nkeys; -ERANGE
+ *     for d.samples >= 2^31; -ERANGE for L != cap.  The reference refuses
+ *     needed > tmp_cap; a frame shorter than its slot is refused too, because
+ *     the whole slot goes on air and the receiver parses the whole slot, so it
+ *     could never verify.
+ *   - Frames sit back to back at byte granularity (any alignment), and their
+ *     neighbours are written at the same time: every byte of d_bytes is stored
+ *     as a byte, so no dword a frame does not wholly own is read and written
+ *     back.  A symbol pair is one 32-bit store when d.sym_offset is even, two
+ *     16-bit stores otherwise.  Bytes of d_bytes and symbols of d_syms_out that
+ *     no frame owns keep their contents; frames must not overlap.
+ *   - d_src is read in aligned dwords that hold at least one byte of the
+ *     frame's FOpts / FRMPayload, never another (so no read leaves the pages
+ *     the source bytes are on).  A frame with neither reads nothing of d_src.
+ * Returns 0 for frames == 0; -EINVAL for a null d_src, d_tx, d_desc, d_keys,
+ * d_bytes or d_status (a null d_syms_out is allowed), symbol_samples == 0,
+ * nkeys == 0, or d_keys / d_tx not 16-byte aligned; -ERANGE for frames >=
+ * 2^31.  All of it before the launch. */
+int lphy_hip_lorawan_build_ragged(const uint8_t* d_src, const lphy_lorawan_tx* d_tx,
+                                  const lphy_ragged_desc* d_desc, size_t frames, size_t symbol_samples,
+                                  const uint8_t* d_keys, size_t nkeys, uint8_t* d_bytes,
+                                  uint16_t* d_syms_out /* may be NULL */, int32_t* d_status, void* stream);
+
+/* Host-only, no device work: h_desc[frames + 1] for the frames of h_tx, packed
+ * back to back: lphy_hip_tx_layout on the lengths L = 12 + fopts_len +
+ * payload_len, so every frame's slot is exactly L bytes.  Returns what
+ * lphy_hip_tx_layout returns, and -EINVAL for a null ctx or a fopts_len > 15. */
+int lphy_hip_lorawan_tx_layout(const lphy_hip_ctx* ctx, const lphy_lorawan_tx* h_tx, size_t frames,
+                               lphy_ragged_desc* h_desc);
+
+typedef struct lphy_lorawan_session { /* one session of the DevAddr lookup */
+    uint32_t devaddr;
+    uint32_t key;                     /* index into d_keys */
+} lphy_lorawan_session;
+
+/* parse_frame's checks on what lphy_hip_demod_ragged(..., mode, LPHY_F_DECODE)
+ * left in d_bytes.  Row f, with d = d_desc[f], is len = out / 2 bytes at
+ * d_bytes + d.sym_offset / 2, where out is lphy_hip_syms_per_frame of d.samples
+ * in `mode`: exactly the bytes that call wrote for the frame.  d_out[f] is the
+ * lphy_lorawan_frame lphy_hip_lorawan_parse_batch gives for that row, and
+ * before anything of the row is read:
+ *   - d.samples >= 2^31: status -ERANGE, the rest of the record zero;
+ *   - with d_meta, d_meta[f].status != 0: that status, the rest zero
+ *     (parse_frame returns decode's error, lorawan.cpp:149; the per-frame
+ *     length statuses of lphy_hip_demod_ragged flow through the same way).
+ *     crc_ok is not consulted, as the reference does not consult it;
+ *   - len < 12 or len > 65535: status -ERANGE, the rest zero.
+ * Which key a frame gets:
+ *   - d_key_index[f], as in lphy_hip_lorawan_parse_batch (an index >= nkeys:
+ *     status -ENOKEY, the rest zero);
+ *   - neither d_key_index nor d_sessions: key 0;
+ *   - d_sessions: found by the row's DevAddr.  The table holds nsessions
+ *     records sorted by devaddr ascending (lphy_hip_lorawan_sessions_check);
+ *     equal DevAddrs are allowed, LoRaWAN does not make them unique.  A
+ *     lower-bound search finds the first record with the row's DevAddr; the
+ *     records with that DevAddr are then tried in table order, the first 8 of
+ *     them at most (a fixed bound, so no table makes a thread spin: records
+ *     past the eighth are not tried).  Of those, records whose key >= nkeys
+ *     are skipped; the first one whose MIC matches wins.  No record, or none
+ *     with a usable key: status -ENOKEY, the header fields and the carried mic
+ *     filled, calc_mic = 0.  Candidates but no match: status -EINVAL, calc_mic
+ *     the first candidate's.  An unsorted table cannot lead outside it; which
+ *     records are then tried is unspecified.
+ * d_key_used[f] (optional) receives the index of the key calc_mic was computed
+ * with (on a session mismatch: the first candidate's), 0xFFFFFFFF when no MIC
+ * was computed.
+ * Returns 0 for frames == 0; -EINVAL for a null d_bytes, d_desc, d_keys or
+ * d_out, nkeys == 0, a mode outside 0..2, symbol_samples == 0, d_keys / d_out
+ * not 16-byte aligned, both d_key_index and d_sessions, or d_sessions with
+ * nsessions == 0; -ERANGE for frames >= 2^31.  All of it before the launch. */
+int lphy_hip_lorawan_parse_ragged(const uint8_t* d_bytes, const lphy_ragged_desc* d_desc, size_t frames,
+                                  size_t symbol_samples, int mode,
+                                  const lphy_frame_meta* d_meta /* may be NULL */, const uint8_t* d_keys,
+                                  size_t nkeys, const uint32_t* d_key_index /* may be NULL */,
+                                  const lphy_lorawan_session* d_sessions /* may be NULL */, size_t nsessions,
+                                  lphy_lorawan_frame* d_out, uint32_t* d_key_used /* may be NULL */,
+                                  void* stream);
+
+/* Host-only: 0 when the table is sorted by devaddr ascending (equal DevAddrs
+ * allowed, n == 0 included), -EINVAL when it is not or is null with n > 0. */
+int lphy_hip_lorawan_sessions_check(const lphy_lorawan_session* h_sessions, size_t n);
 
 #ifdef __cplusplus
 }

@@ -12,6 +12,7 @@
 #include "lphy_tx.h"
 #include "lphy_route.h"
 #include "lphy_stage_plan.h"
+#include "lphy_lorawan_ragged.h"
 #include "lphy_testing.h"
 
 #include <cmath>
@@ -1036,6 +1037,17 @@ int lphy_hip_tx_layout(const lphy_hip_ctx* c, const uint64_t* h_len_bytes, size_
     if (!c) return -EINVAL;
     return tx_layout((uint64_t)c->N * c->osr, h_len_bytes, frames, h_desc);
 }
+
+// lphy_hip_tx_layout on the lengths of the LoRaWAN frames of h_tx
+// (lphy_lorawan_ragged.h); the calls that build and parse them are context-free
+// (lphy_lorawan.hip) and take N * osr from lphy_hip_symbol_samples.
+int lphy_hip_lorawan_tx_layout(const lphy_hip_ctx* c, const lphy_lorawan_tx* h_tx, size_t frames,
+                               lphy_ragged_desc* h_desc) {
+    if (!c) return -EINVAL;
+    return lw_tx_layout((uint64_t)c->N * c->osr, h_tx, frames, h_desc);
+}
+
+size_t lphy_hip_symbol_samples(const lphy_hip_ctx* c) { return c ? (size_t)c->N * c->osr : 0; }
 
 namespace {
 // The argument checks the three forms share, in the header's order (`src`: the

@@ -16,6 +16,14 @@
 // derived in the prologue from the field inverse, not loaded.  Round keys
 // (44 dwords) live in VGPRs.  Each workgroup loops over frames
 // (grid-stride), so the 32 KiB table build is paid once per workgroup.
+//
+// The same two jobs on the lphy_ragged_desc table of the ragged PHY calls:
+// build_frame (lorawan.cpp:100-136) for frames of different lengths packed at
+// byte granularity (k_lw_build: header, FOpts and FRMPayload gathered, MIC
+// appended, lora_encode's symbols on request), and parse_frame's checks on
+// what lphy_hip_demod_ragged left, with the key found by DevAddr in a sorted
+// session table (k_lw_parse_ragged).  The TU knows no context: the samples of
+// a symbol are an argument.
 #include <hip/hip_runtime.h>
 
 #include <cerrno>
@@ -25,8 +33,11 @@
 #include <mutex>
 
 #include "../../include/lphy_hip.h"
+#include "lphy_lorawan_ragged.h"
 
 namespace {
+
+using namespace lphy;
 
 #define LW_OK(x)                                                           \
     do {                                                                   \
@@ -164,9 +175,12 @@ __device__ __forceinline__ void load16(const uint8_t* p, unsigned n, uint32_t w[
     }
 }
 
-// lorawan.cpp:35-98 for one frame.
-__device__ uint32_t frame_mic(const Tab& tb, const uint32_t key[4], bool uplink, uint32_t devaddr, uint32_t fcnt,
-                              const uint8_t* data, uint32_t len) {
+// lorawan.cpp:35-98 for one frame of `len` bytes, which load(off, have, m)
+// hands over 16 at a time, in order: bytes off .. off + have - 1 (1 <= have <=
+// 16, off a multiple of 16) as load16 gives them.
+template <class Load>
+__device__ uint32_t frame_mic_from(const Tab& tb, const uint32_t key[4], bool uplink, uint32_t devaddr,
+                                   uint32_t fcnt, uint32_t len, Load load) {
     uint32_t rk[44];
     expand_key(tb, key, rk);
     uint32_t K1[4] = {0, 0, 0, 0}, K2[4];
@@ -188,7 +202,7 @@ __device__ uint32_t frame_mic(const Tab& tb, const uint32_t key[4], bool uplink,
     for (uint32_t b = 1; b < nblk; ++b) {
         const uint32_t have = total - 16 * b < 16 ? total - 16 * b : 16;
         uint32_t m[4];
-        load16(data + 16 * (b - 1), have, m);
+        load(16 * (b - 1), have, m);
         if (b + 1 == nblk) {
             if (have < 16) m[have >> 2] |= 0x80u << (8 * (have & 3));
             const uint32_t* K = have == 16 ? K1 : K2;
@@ -200,6 +214,13 @@ __device__ uint32_t frame_mic(const Tab& tb, const uint32_t key[4], bool uplink,
         encrypt(tb, rk, X);
     }
     return X[0];  // tag bytes 0-3, little-endian (lorawan.cpp:94-97)
+}
+
+// the same for `len` bytes in memory at `data`
+__device__ uint32_t frame_mic(const Tab& tb, const uint32_t key[4], bool uplink, uint32_t devaddr, uint32_t fcnt,
+                              const uint8_t* data, uint32_t len) {
+    return frame_mic_from(tb, key, uplink, devaddr, fcnt, len,
+                          [data](uint32_t off, uint32_t have, uint32_t m[4]) { load16(data + off, have, m); });
 }
 
 __device__ __forceinline__ void load_key(const uint8_t* keys, uint32_t idx, uint32_t k[4]) {
@@ -234,6 +255,126 @@ __global__ void __launch_bounds__(kThreads) k_lw_mic(uint8_t* bytes, const lphy_
     }
 }
 
+// k_lw_build: one frame of the table per thread.  The frame is handed to the
+// CMAC 16 bytes at a time as it is gathered (the 8 header bytes from the
+// record, then FOpts and FRMPayload from src through load16), and every block
+// is stored on its way through; the MIC follows.  d_bytes gets byte stores
+// only: a frame starts and ends at any byte, and the dwords at its ends belong
+// partly to neighbours other threads write at the same time.
+__global__ void __launch_bounds__(kThreads) k_lw_build(const uint8_t* src, const lphy_lorawan_tx* tx,
+                                                       const lphy_ragged_desc* desc, unsigned long long frames,
+                                                       unsigned long long step, const uint8_t* keys,
+                                                       unsigned long long nkeys, uint8_t* bytes, uint16_t* syms,
+                                                       int32_t* status) {
+    extern __shared__ uint32_t lds[];
+    build_table(lds);
+    const Tab tb = lane_tab(lds);
+    for (unsigned long long f = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; f < frames;
+         f += (unsigned long long)gridDim.x * blockDim.x) {
+        const uint4* tp = reinterpret_cast<const uint4*>(tx + f);
+        const uint4 a = tp[0], b = tp[1];
+        const unsigned long long src_offset = a.x | (unsigned long long)a.y << 32;
+        const uint32_t devaddr = a.z, key = a.w, payload_len = b.x;
+        const uint32_t fcnt = b.y & 0xFFFFu, mtype = (b.y >> 16) & 0xFFu, major = b.y >> 24;
+        const uint32_t fctrl = b.z & 0xFFu, fol = (b.z >> 8) & 0xFFu;
+        const unsigned long long samples = desc[f].samples, sym_offset = desc[f].sym_offset;
+        const unsigned long long L = lw_tx_len(fol, payload_len);
+        if (fol > 15 || mtype > 7) {
+            status[f] = -EINVAL;
+        } else if (key >= nkeys) {
+            status[f] = -ENOKEY;
+        } else if (samples >= kRaggedMaxSamples || L != lw_slot_bytes(samples, step)) {
+            status[f] = -ERANGE;
+        } else {  // L < 2^30
+            uint8_t* dst = bytes + sym_offset / 2;
+            uint16_t* so = syms ? syms + sym_offset : nullptr;
+            const bool pair = (sym_offset & 1) == 0;  // a symbol pair is an aligned dword of the slot
+            // `n` bytes of w to the frame at byte `off`, and their symbols (LoRaEncoder.cpp:6-18)
+            auto put = [&](uint32_t off, uint32_t n, const uint32_t w[4]) {
+#pragma unroll
+                for (uint32_t i = 0; i < 16; ++i) {
+                    if (i >= n) continue;
+                    const uint32_t v = byte_of(w[i >> 2], i & 3);
+                    dst[off + i] = (uint8_t)v;
+                    if (so) {
+                        const uint32_t e = lw_encode_byte(v);
+                        uint16_t* p = so + 2ull * (off + i);
+                        if (pair) *reinterpret_cast<uint32_t*>(p) = e;
+                        else p[0] = (uint16_t)e, p[1] = (uint16_t)(e >> 16);
+                    }
+                }
+            };
+            const uint32_t h0 = (mtype << 5 | (major & 3)) | devaddr << 8;
+            const uint32_t h1 = devaddr >> 24 | ((fctrl & 0xF0) | fol) << 8 | fcnt << 16;
+            const uint8_t* body = src + src_offset;
+            uint32_t k[4];
+            load_key(keys, key, k);
+            const uint32_t m = frame_mic_from(tb, k, (mtype & 1) == 0, devaddr, fcnt, (uint32_t)L - 4,
+                                              [&](uint32_t off, uint32_t have, uint32_t w[4]) {
+                                                  if (off) {
+                                                      load16(body + (off - 8), have, w);
+                                                  } else {  // the header, then the first 8 bytes of the body
+                                                      uint32_t t[4] = {0, 0, 0, 0};
+                                                      if (have > 8) load16(body, have - 8, t);
+                                                      w[0] = h0, w[1] = h1, w[2] = t[0], w[3] = t[1];
+                                                  }
+                                                  put(off, have, w);
+                                              });
+            const uint32_t mw[4] = {m, 0, 0, 0};
+            put((uint32_t)L - 4, 4, mw);
+            status[f] = (int32_t)(2 * L);
+        }
+    }
+}
+
+// What parse_frame reads of a row before the MIC is known (lorawan.cpp:152-158).
+struct RowHead {
+    uint32_t mhdr, devaddr, fctrl, fcnt, mic;
+};
+
+__device__ __forceinline__ RowHead row_head(const uint8_t* row, uint32_t len) {
+    uint32_t h[4], t[4];
+    load16(row, 8, h);
+    load16(row + len - 4, 4, t);
+    return RowHead{h[0] & 0xFF, (h[0] >> 8) | (h[1] << 24), (h[1] >> 8) & 0xFF, h[1] >> 16, t[0]};
+}
+
+__device__ __forceinline__ uint32_t row_mic(const Tab& tb, const uint8_t* keys, uint32_t kidx, const RowHead& h,
+                                            const uint8_t* row, uint32_t len) {
+    uint32_t k[4];
+    load_key(keys, kidx, k);
+    return frame_mic(tb, k, ((h.mhdr >> 5) & 1) == 0, h.devaddr, h.fcnt, row, len - 4);
+}
+
+// The header fields and the carried MIC of the record.
+__device__ __forceinline__ void row_fields(const RowHead& h, uint32_t rec[8]) {
+    rec[1] = h.devaddr, rec[2] = h.mic;
+    rec[6] = h.fcnt | h.mhdr << 16 | h.fctrl << 24;
+    rec[7] = h.fctrl & 0x0F;
+}
+
+// The rest once the MIC is computed (lorawan.cpp:161-176).
+__device__ __forceinline__ void row_verdict(const RowHead& h, uint32_t calc, uint32_t len, uint32_t rec[8]) {
+    const uint32_t fol = h.fctrl & 0x0F;
+    row_fields(h, rec);
+    rec[3] = calc;
+    if (h.mic != calc) {
+        rec[0] = (uint32_t)-EINVAL;
+    } else if (8 + fol > len - 4) {
+        rec[0] = (uint32_t)-ERANGE;
+    } else {
+        rec[4] = 8 + fol;
+        rec[5] = len - 12 - fol;
+        rec[0] = rec[5];
+    }
+}
+
+__device__ __forceinline__ void store_record(lphy_lorawan_frame* out, const uint32_t rec[8]) {
+    uint4* o = reinterpret_cast<uint4*>(out);
+    o[0] = make_uint4(rec[0], rec[1], rec[2], rec[3]);
+    o[1] = make_uint4(rec[4], rec[5], rec[6], rec[7]);
+}
+
 // lorawan.cpp:150-176 on one row of decoded bytes.
 __global__ void __launch_bounds__(kThreads) k_lw_parse(const uint8_t* bytes, unsigned long long frames,
                                                        unsigned long long stride, const uint32_t* lens,
@@ -256,30 +397,68 @@ __global__ void __launch_bounds__(kThreads) k_lw_parse(const uint8_t* bytes, uns
         } else if (kidx >= nkeys) {
             rec[0] = (uint32_t)-ENOKEY;
         } else {
-            uint32_t h[4], t[4];
-            load16(row, 8, h);
-            load16(row + len - 4, 4, t);
-            const uint32_t mhdr = h[0] & 0xFF, devaddr = (h[0] >> 8) | (h[1] << 24);
-            const uint32_t fctrl = (h[1] >> 8) & 0xFF, fcnt = h[1] >> 16, fol = fctrl & 0x0F;
-            uint32_t k[4];
-            load_key(keys, kidx, k);
-            const uint32_t calc = frame_mic(tb, k, ((mhdr >> 5) & 1) == 0, devaddr, fcnt, row, len - 4);
-            rec[1] = devaddr, rec[2] = t[0], rec[3] = calc;
-            rec[6] = fcnt | mhdr << 16 | fctrl << 24;
-            rec[7] = fol;
-            if (t[0] != calc) {
-                rec[0] = (uint32_t)-EINVAL;
-            } else if (8 + fol > len - 4) {
-                rec[0] = (uint32_t)-ERANGE;
+            const RowHead h = row_head(row, len);
+            row_verdict(h, row_mic(tb, keys, kidx, h, row, len), len, rec);
+        }
+        store_record(out + f, rec);
+    }
+}
+
+// The same on the rows lphy_hip_demod_ragged left: row f is the decoded bytes
+// of the frame's output symbols at sym_offset / 2.  The key is key_index[f],
+// key 0, or - with a session table - the first of the up to kLwMaxCandidates
+// records with the row's DevAddr whose MIC matches.
+__global__ void __launch_bounds__(kThreads) k_lw_parse_ragged(
+    const uint8_t* bytes, const lphy_ragged_desc* desc, unsigned long long frames, unsigned long long step, int mode,
+    const lphy_frame_meta* meta, const uint8_t* keys, unsigned long long nkeys, const uint32_t* key_index,
+    const lphy_lorawan_session* sessions, unsigned long long nsessions, lphy_lorawan_frame* out,
+    uint32_t* key_used) {
+    extern __shared__ uint32_t lds[];
+    build_table(lds);
+    const Tab tb = lane_tab(lds);
+    for (unsigned long long f = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; f < frames;
+         f += (unsigned long long)gridDim.x * blockDim.x) {
+        const unsigned long long samples = desc[f].samples, sym_offset = desc[f].sym_offset;
+        uint32_t rec[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        uint32_t used = kLwNoKey;
+        const unsigned long long len64 = samples < kRaggedMaxSamples ? ragged_out_syms(samples / step, mode) / 2 : 0;
+        const uint32_t kidx = key_index ? key_index[f] : 0u;
+        int32_t st = 0;
+        if (samples >= kRaggedMaxSamples) {
+            rec[0] = (uint32_t)-ERANGE;
+        } else if (meta && (st = meta[f].status) != 0) {  // decode's error (lorawan.cpp:149)
+            rec[0] = (uint32_t)st;
+        } else if (len64 < 12 || len64 > 65535u) {
+            rec[0] = (uint32_t)-ERANGE;
+        } else if (!sessions && kidx >= nkeys) {
+            rec[0] = (uint32_t)-ENOKEY;
+        } else {
+            const uint32_t len = (uint32_t)len64;
+            const uint8_t* row = bytes + sym_offset / 2;
+            const RowHead h = row_head(row, len);
+            // the candidates: the one key, or the records with the row's DevAddr
+            const unsigned long long first = sessions ? lw_lower_bound(sessions, nsessions, h.devaddr) : 0;
+            uint32_t calc = 0;
+            for (unsigned c = 0; c < (sessions ? kLwMaxCandidates : 1u); ++c) {
+                uint32_t k = kidx;
+                if (sessions) {
+                    if (first + c >= nsessions || sessions[first + c].devaddr != h.devaddr) break;
+                    k = sessions[first + c].key;
+                    if (k >= nkeys) continue;
+                }
+                const uint32_t m = row_mic(tb, keys, k, h, row, len);
+                if (used == kLwNoKey || m == h.mic) used = k, calc = m;  // the first, then the match
+                if (m == h.mic) break;
+            }
+            if (used == kLwNoKey) {
+                row_fields(h, rec);
+                rec[0] = (uint32_t)-ENOKEY;
             } else {
-                rec[4] = 8 + fol;
-                rec[5] = len - 12 - fol;
-                rec[0] = rec[5];
+                row_verdict(h, calc, len, rec);
             }
         }
-        uint4* o = reinterpret_cast<uint4*>(out + f);
-        o[0] = make_uint4(rec[0], rec[1], rec[2], rec[3]);
-        o[1] = make_uint4(rec[4], rec[5], rec[6], rec[7]);
+        store_record(out + f, rec);
+        if (key_used) key_used[f] = used;
     }
 }
 
@@ -294,6 +473,7 @@ constexpr size_t kLds = 256 * kCopies * sizeof(uint32_t);  // 32 KiB
 
 static_assert(sizeof(lphy_lorawan_desc) == 32, "descriptor layout");
 static_assert(sizeof(lphy_lorawan_frame) == 32, "record layout");
+static_assert(sizeof(lphy_lorawan_tx) == 32 && sizeof(lphy_lorawan_session) == 8, "ragged record layouts");
 
 extern "C" {
 
@@ -322,6 +502,43 @@ int lphy_hip_lorawan_parse_batch(const uint8_t* d_bytes, size_t frames, size_t s
                        (unsigned long long)nkeys, d_key_index, d_out);
     LW_OK(hipGetLastError());
     return 0;
+}
+
+int lphy_hip_lorawan_build_ragged(const uint8_t* d_src, const lphy_lorawan_tx* d_tx, const lphy_ragged_desc* d_desc,
+                                  size_t frames, size_t symbol_samples, const uint8_t* d_keys, size_t nkeys,
+                                  uint8_t* d_bytes, uint16_t* d_syms_out, int32_t* d_status, void* stream) {
+    if (!frames) return 0;
+    if (!d_src || !d_tx || !d_desc || !d_keys || !d_bytes || !d_status || !symbol_samples || !nkeys) return -EINVAL;
+    if (reinterpret_cast<uintptr_t>(d_keys) & 15 || reinterpret_cast<uintptr_t>(d_tx) & 15) return -EINVAL;
+    if (frames > 0x7fffffffULL) return -ERANGE;
+    hipLaunchKernelGGL(k_lw_build, dim3(grid_for(frames)), dim3(kThreads), kLds, (hipStream_t)stream, d_src, d_tx,
+                       d_desc, (unsigned long long)frames, (unsigned long long)symbol_samples, d_keys,
+                       (unsigned long long)nkeys, d_bytes, d_syms_out, d_status);
+    LW_OK(hipGetLastError());
+    return 0;
+}
+
+int lphy_hip_lorawan_parse_ragged(const uint8_t* d_bytes, const lphy_ragged_desc* d_desc, size_t frames,
+                                  size_t symbol_samples, int mode, const lphy_frame_meta* d_meta,
+                                  const uint8_t* d_keys, size_t nkeys, const uint32_t* d_key_index,
+                                  const lphy_lorawan_session* d_sessions, size_t nsessions,
+                                  lphy_lorawan_frame* d_out, uint32_t* d_key_used, void* stream) {
+    if (!frames) return 0;
+    if (!d_bytes || !d_desc || !d_keys || !d_out || !nkeys || !symbol_samples) return -EINVAL;
+    if (mode < 0 || mode > 2) return -EINVAL;
+    if (reinterpret_cast<uintptr_t>(d_keys) & 15 || reinterpret_cast<uintptr_t>(d_out) & 15) return -EINVAL;
+    if ((d_key_index && d_sessions) || (d_sessions && !nsessions)) return -EINVAL;
+    if (frames > 0x7fffffffULL) return -ERANGE;
+    hipLaunchKernelGGL(k_lw_parse_ragged, dim3(grid_for(frames)), dim3(kThreads), kLds, (hipStream_t)stream, d_bytes,
+                       d_desc, (unsigned long long)frames, (unsigned long long)symbol_samples, mode, d_meta, d_keys,
+                       (unsigned long long)nkeys, d_key_index, d_sessions,
+                       (unsigned long long)(d_sessions ? nsessions : 0), d_out, d_key_used);
+    LW_OK(hipGetLastError());
+    return 0;
+}
+
+int lphy_hip_lorawan_sessions_check(const lphy_lorawan_session* h_sessions, size_t n) {
+    return lw_sessions_check(h_sessions, n);
 }
 
 int lphy_hip_lorawan_mic_host(int device, const uint8_t key[16], int uplink, uint32_t devaddr, uint32_t fcnt,

@@ -1,0 +1,85 @@
+// lphy_lorawan_ragged.h — what the LoRaWAN calls on a ragged table
+// (lphy_hip_lorawan_build_ragged, lphy_hip_lorawan_parse_ragged) share between
+// the kernels of lphy_lorawan.hip and the host: the frame geometry, the
+// lower-bound search of the session table, encodeHamming84sx of a byte, and
+// the two host-only helpers (lphy_hip_lorawan_tx_layout,
+// lphy_hip_lorawan_sessions_check).  Plain C++ with LPHY_LW_HD in front of what
+// the kernels call too, so the CPU tests compile it alone
+// (tests/cpp/lorawan_ragged_check.cpp).
+#pragma once
+#include <cerrno>
+#include <cstddef>
+#include <cstdint>
+#include <new>
+#include <vector>
+
+#include "lphy_ragged_layout.h"
+
+#if defined(__HIPCC__)
+#define LPHY_LW_HD __host__ __device__
+#else
+#define LPHY_LW_HD
+#endif
+
+namespace lphy {
+
+constexpr unsigned kLwMaxCandidates = 8;  // session records tried per frame
+constexpr uint32_t kLwNoKey = 0xFFFFFFFFu;
+
+// MHDR .. MIC of a frame to build: 12 + FOpts + FRMPayload (lorawan.cpp:108)
+LPHY_LW_HD constexpr uint64_t lw_tx_len(uint32_t fopts_len, uint32_t payload_len) {
+    return 12u + uint64_t(fopts_len) + payload_len;
+}
+
+// bytes a frame of `samples` samples carries on air: its data symbols / 2
+LPHY_LW_HD constexpr uint64_t lw_slot_bytes(uint64_t samples, uint64_t step) {
+    return samples / step < 2 ? 0 : (samples / step - 2) / 2;
+}
+
+// first record whose devaddr is not below `devaddr` (n when there is none) of
+// a table sorted by devaddr ascending.  At most 64 steps whatever the table
+// holds, sorted or not.
+LPHY_LW_HD inline size_t lw_lower_bound(const lphy_lorawan_session* s, size_t n, uint32_t devaddr) {
+    size_t lo = 0, hi = n;
+    while (lo < hi) {
+        const size_t mid = lo + (hi - lo) / 2;
+        if (s[mid].devaddr < devaddr) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// encodeHamming84sx (LoRaCodes.hpp:229-242) of both nibbles of a byte, as
+// lora_encode orders them (LoRaEncoder.cpp:6-18): the high nibble's symbol in
+// bits 0-15, the low nibble's in bits 16-31
+LPHY_LW_HD constexpr uint32_t lw_enc84(uint32_t x) {
+    return (x & 0xF) | (((x ^ x >> 1 ^ x >> 2) & 1) << 4) | (((x >> 1 ^ x >> 2 ^ x >> 3) & 1) << 5) |
+           (((x ^ x >> 1 ^ x >> 3) & 1) << 6) | (((x ^ x >> 2 ^ x >> 3) & 1) << 7);
+}
+LPHY_LW_HD constexpr uint32_t lw_encode_byte(uint32_t b) { return lw_enc84((b >> 4) & 0xF) | lw_enc84(b & 0xF) << 16; }
+
+// lphy_hip_lorawan_sessions_check
+inline int lw_sessions_check(const lphy_lorawan_session* s, size_t n) {
+    if (n && !s) return -EINVAL;
+    for (size_t i = 1; i < n; ++i)
+        if (s[i].devaddr < s[i - 1].devaddr) return -EINVAL;
+    return 0;
+}
+
+// lphy_hip_lorawan_tx_layout: tx_layout on the frames' lengths
+inline int lw_tx_layout(uint64_t step, const lphy_lorawan_tx* h_tx, size_t frames, lphy_ragged_desc* h_desc) {
+    if (!h_desc || (frames && !h_tx) || step == 0) return -EINVAL;
+    std::vector<uint64_t> len;
+    try {
+        len.resize(frames);
+    } catch (const std::bad_alloc&) {
+        return -ENOMEM;
+    }
+    for (size_t f = 0; f < frames; ++f) {
+        if (h_tx[f].fopts_len > 15) return -EINVAL;
+        len[f] = lw_tx_len(h_tx[f].fopts_len, h_tx[f].payload_len);
+    }
+    return tx_layout(step, len.data(), frames, h_desc);
+}
+
+}  // namespace lphy

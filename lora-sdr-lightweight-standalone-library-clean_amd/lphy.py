@@ -115,6 +115,8 @@ EXPORTS = (
     "lphy_hip_modulate_ragged", "lphy_hip_tx_ragged", "lphy_hip_tx_ragged_host", "lphy_hip_tx_layout",
     "lphy_hip_estimate_ragged", "lphy_hip_estimate_ragged_host",
     "lphy_hip_detect_ragged", "lphy_hip_detect_ragged_host",
+    "lphy_hip_symbol_samples", "lphy_hip_lorawan_build_ragged", "lphy_hip_lorawan_tx_layout",
+    "lphy_hip_lorawan_parse_ragged", "lphy_hip_lorawan_sessions_check",
 )
 
 WHITEN_SX1232, WHITEN_SX1272, WHITEN_SX1272_LFSR = 0, 1, 2
@@ -210,6 +212,13 @@ def load(path: Path | None = None) -> C.CDLL:
     L.lphy_hip_lorawan_parse_batch.argtypes = [_vp, _sz, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp]
     L.lphy_hip_lorawan_mic_host.argtypes = [C.c_int, _vp, C.c_int, C.c_uint32, C.c_uint32, _vp, _sz,
                                             C.POINTER(C.c_uint32)]
+    L.lphy_hip_symbol_samples.argtypes = [_vp]
+    L.lphy_hip_symbol_samples.restype = _sz
+    L.lphy_hip_lorawan_build_ragged.argtypes = [_vp, _vp, _vp, _sz, _sz, _vp, _sz, _vp, _vp, _vp, _vp]
+    L.lphy_hip_lorawan_tx_layout.argtypes = [_vp, _vp, _sz, _vp]
+    L.lphy_hip_lorawan_parse_ragged.argtypes = [_vp, _vp, _sz, _sz, C.c_int, _vp, _vp, _sz, _vp, _vp, _sz, _vp,
+                                                _vp, _vp]
+    L.lphy_hip_lorawan_sessions_check.argtypes = [_vp, _sz]
     _LIBS[str(path)] = L
     return L
 
@@ -281,6 +290,21 @@ class Demodulator:
 
     def syms_per_frame(self, frame_samples: int, mode: int) -> int:
         return self.lib.lphy_hip_syms_per_frame(self.ctx, frame_samples, mode)
+
+    def symbol_samples(self) -> int:
+        """N * osr: the samples of one symbol (lphy_hip_symbol_samples), what
+        lorawan_build_ragged / lorawan_parse_ragged take for this context."""
+        return int(self.lib.lphy_hip_symbol_samples(self.ctx))
+
+    def lorawan_tx_layout(self, tx) -> np.ndarray:
+        """Descriptors (RAGGED_DESC_DTYPE, len(tx) + 1 records) of the LoRaWAN
+        frames of `tx` (LORAWAN_TX_DTYPE), packed back to back: tx_layout on
+        12 + fopts_len + payload_len bytes each (lphy_hip_lorawan_tx_layout)."""
+        t = np.ascontiguousarray(tx, LORAWAN_TX_DTYPE).reshape(-1)
+        desc = np.zeros(t.size + 1, RAGGED_DESC_DTYPE)
+        _chk(self.lib.lphy_hip_lorawan_tx_layout(self.ctx, t.ctypes.data if t.size else None, t.size,
+                                                 desc.ctypes.data), "lphy_hip_lorawan_tx_layout")
+        return desc
 
     # --- device batch API (torch tensors) --------------------------------
     def demod_batch(self, iq, frames, frame_samples, syms, meta, mode, flags=0,
@@ -867,6 +891,64 @@ def lorawan_parse_batch(data, frames, stride, length, keys, out, lens=None, key_
                                              frames, stride, pl, length, _dptr(keys, "keys", nkeys * 16, 1),
                                              nkeys, pk, _dptr(out, "out", frames * 32), stream),
          "lphy_hip_lorawan_parse_batch")
+
+
+# lphy_lorawan_tx / lphy_lorawan_session (include/lphy_hip.h): LoRaWAN on the
+# ragged table
+LORAWAN_TX_DTYPE = np.dtype([("src_offset", "<u8"), ("devaddr", "<u4"), ("key", "<u4"), ("payload_len", "<u4"),
+                             ("fcnt", "<u2"), ("mtype", "u1"), ("major", "u1"), ("fctrl", "u1"),
+                             ("fopts_len", "u1"), ("reserved", "u1", 6)])
+LORAWAN_SESSION_DTYPE = np.dtype([("devaddr", "<u4"), ("key", "<u4")])
+assert LORAWAN_TX_DTYPE.itemsize == 32 and LORAWAN_SESSION_DTYPE.itemsize == 8
+LW_NO_KEY = 0xFFFFFFFF
+
+
+def lorawan_sessions_check(sessions) -> bool:
+    """True when `sessions` (LORAWAN_SESSION_DTYPE, host) is sorted by devaddr
+    ascending, as lorawan_parse_ragged's lookup needs it."""
+    s = np.ascontiguousarray(sessions, LORAWAN_SESSION_DTYPE).reshape(-1)
+    return load().lphy_hip_lorawan_sessions_check(s.ctypes.data if s.size else None, s.size) == 0
+
+
+def lorawan_build_ragged(src, tx, desc, frames, symbol_samples, keys, data, status, syms_out=None, stream=None,
+                         src_bytes=None, out_syms=None):
+    """build_frame for every frame of a ragged table (lphy_hip_lorawan_build_ragged),
+    device tensors throughout.  src: FOpts then FRMPayload of frame f at
+    tx[f]["src_offset"]; tx: frames LORAWAN_TX_DTYPE records; desc: frames + 1
+    RAGGED_DESC_DTYPE records (Demodulator.lorawan_tx_layout); symbol_samples:
+    Demodulator.symbol_samples(); data: the frames' bytes at sym_offset // 2;
+    syms_out (optional): their symbols at sym_offset; status: int32 per frame,
+    2 * bytes or a negative errno.  src_bytes / out_syms: the extents the
+    records span (checked against the tensors).  Asynchronous."""
+    nkeys = keys.numel() // 16
+    ps = _dptr(syms_out, "syms_out", (out_syms or 0) * 2, 2) if syms_out is not None else None
+    _chk(load().lphy_hip_lorawan_build_ragged(
+        _dptr(src, "src", src_bytes or 0, 1), _dptr(tx, "tx", frames * 32), _dptr(desc, "desc", (frames + 1) * 32),
+        frames, symbol_samples, _dptr(keys, "keys", nkeys * 16, 1), nkeys,
+        _dptr(data, "data", ((out_syms or 0) + 1) // 2, 1), ps, _dptr(status, "status", frames * 4, 4), stream),
+        "lphy_hip_lorawan_build_ragged")
+
+
+def lorawan_parse_ragged(data, desc, frames, symbol_samples, mode, keys, out, meta=None, key_index=None,
+                         sessions=None, key_used=None, stream=None, out_syms=None):
+    """parse_frame's checks on the bytes demod_ragged(mode, F_DECODE) left at
+    sym_offset // 2 (lphy_hip_lorawan_parse_ragged), device tensors throughout.
+    out: frames * 32 bytes (LORAWAN_FRAME_DTYPE); meta (optional): the
+    demodulator's records, whose nonzero status becomes the frame's; the key is
+    key_index[f], key 0, or found by DevAddr in `sessions` (LORAWAN_SESSION_DTYPE
+    records sorted by devaddr; at most one of the two); key_used (optional):
+    int32 per frame, LW_NO_KEY where no MIC was computed.  out_syms: the symbol
+    extent the descriptors span (checked against `data`).  Asynchronous."""
+    nkeys = keys.numel() // 16
+    pm = _dptr(meta, "meta", frames * 32) if meta is not None else None
+    pk = _dptr(key_index, "key_index", frames * 4, 4) if key_index is not None else None
+    nsess = sessions.numel() * sessions.element_size() // 8 if sessions is not None else 0
+    pse = _dptr(sessions, "sessions", nsess * 8) if sessions is not None else None
+    pu = _dptr(key_used, "key_used", frames * 4, 4) if key_used is not None else None
+    _chk(load().lphy_hip_lorawan_parse_ragged(
+        _dptr(data, "data", ((out_syms or 0) + 1) // 2, 1), _dptr(desc, "desc", (frames + 1) * 32), frames,
+        symbol_samples, mode, pm, _dptr(keys, "keys", nkeys * 16, 1), nkeys, pk, pse, nsess,
+        _dptr(out, "out", frames * 32), pu, stream), "lphy_hip_lorawan_parse_ragged")
 
 
 def lorawan_mic(key, uplink, devaddr, fcnt, data, device=0):
