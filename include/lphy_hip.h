@@ -47,6 +47,10 @@
  *   lphy_hip_lorawan_parse_ragged lorawan::parse_frame src/lorawan/lorawan.cpp:138-177
  *                          for frames of different lengths on that table, the
  *                          key found by DevAddr (lphy_lorawan_session)
+ *   lphy_hip_lorawan_crypt_batch      no reference function: the FRMPayload
+ *   lphy_hip_lorawan_crypt_tx_ragged  cipher of LoRaWAN 1.0.x 4.3.3 on byte
+ *   lphy_hip_lorawan_crypt_rx_ragged  ranges, in front of build_ragged and
+ *                          behind parse_ragged on that table
  *
  * Batch layout in HBM:
  *   IQ      interleaved float32 (I,Q) = std::complex<float>, frame f at
@@ -781,7 +785,10 @@ int lphy_hip_lorawan_mic_host(int device, const uint8_t key[16], int uplink, uin
  * then a chain of launches on one stream with no host read of the table:
  *   receive   lphy_hip_estimate_ragged -> lphy_hip_compensate_ragged ->
  *             lphy_hip_demod_ragged(LPHY_F_DECODE) -> lphy_hip_lorawan_parse_ragged
- *   transmit  lphy_hip_lorawan_build_ragged -> lphy_hip_tx_ragged
+ *             -> lphy_hip_lorawan_crypt_rx_ragged
+ *   transmit  lphy_hip_lorawan_crypt_tx_ragged -> lphy_hip_lorawan_build_ragged
+ *             -> lphy_hip_tx_ragged
+ * (the two crypt calls, the FRMPayload cipher, are described further down).
  * Neither call takes a context: symbol_samples is N * osr of the context whose
  * calls share the table (lphy_hip_symbol_samples).  Keys as above: 16-byte
  * records at d_keys, 16-byte aligned.  Both calls are one launch, asynchronous
@@ -899,6 +906,87 @@ int lphy_hip_lorawan_parse_ragged(const uint8_t* d_bytes, const lphy_ragged_desc
 /* Host-only: 0 when the table is sorted by devaddr ascending (equal DevAddrs
  * allowed, n == 0 included), -EINVAL when it is not or is null with n > 0. */
 int lphy_hip_lorawan_sessions_check(const lphy_lorawan_session* h_sessions, size_t n);
+
+/* ------------------------------------------------------------------------
+ * The FRMPayload cipher (LoRaWAN 1.0.x 4.3.3), an extension beside
+ * compute_mic: the reference sends Frame::payload as given.  For a range of
+ * len bytes, block A_i (i = 1 .. ceil(len / 16)) is B0 of compute_mic
+ * (lorawan.cpp:46-58) with byte 0 = 0x01 and byte 15 = i:
+ *   01 | 00 00 00 00 | dir (0 up, 1 down) | DevAddr LE | FCnt LE (32 bit) | 00 | i
+ * S_i = AES128(K, A_i), and byte j of the range becomes byte ^ S_(j/16+1)[j%16].
+ * The operation is its own inverse.  i is one byte: a range of more than 4080
+ * bytes is refused.
+ *
+ * d_keys is the table of the keys that cipher payloads (AppSKey in practice),
+ * 16-byte records, 16-byte aligned, indexed like the NwkSKey table given to
+ * build and parse, so one session index serves both.  The three device forms
+ * are one launch each, asynchronous on `stream`, allocate nothing on the device
+ * and read no table on the host.  A group of lanes shares a range and takes its
+ * 16-byte blocks in turn.  Ranges sit at any byte and their neighbours are
+ * written at the same time: bytes in front of a block's first aligned dword and
+ * behind its last whole one are stored as bytes, the dwords a block fills as
+ * dwords, and nothing is read and written back.  Reads are aligned dwords that
+ * hold at least one byte of the range.  Ranges must not overlap.  d_status
+ * (optional) receives one int32 per record.
+ * All three return 0 for a zero count; -EINVAL for a null required pointer,
+ * nkeys == 0, d_keys or the 32-byte records (d_desc of the batch form, d_tx,
+ * d_parsed) not 16-byte aligned, skip > 1, symbol_samples == 0 or a mode outside
+ * 0..2; -ERANGE for a count >= 2^31.  All of it before the launch.
+ * --------------------------------------------------------------------- */
+
+/* Job i ciphers d_bytes[offset .. offset + len) in place with devaddr, fcnt (all
+ * 32 bits), key and uplink of d_desc[i].  d_status[i]: 0; -ENOKEY for key >=
+ * nkeys; -ERANGE for len > 4080.  A refused job writes nothing else; len == 0
+ * writes nothing and gives 0. */
+int lphy_hip_lorawan_crypt_batch(uint8_t* d_bytes, const lphy_lorawan_desc* d_desc, size_t jobs,
+                                 const uint8_t* d_keys, size_t nkeys, int32_t* d_status /* may be NULL */,
+                                 void* stream);
+
+/* Before lphy_hip_lorawan_build_ragged, on the same stream, d_src and d_tx:
+ * ciphers the FRMPayload of every frame where build will read it.  Frame f,
+ * with t = d_tx[f]: the range is the t.payload_len - skip bytes at d_src +
+ * t.src_offset + t.fopts_len + skip (nothing when payload_len <= skip), with
+ * t.devaddr, t.fcnt widened with zeros as build widens it for B0, uplink =
+ * (t.mtype & 1) == 0 and the key d_keys[t.key].  skip is 0 or 1: with 1 the
+ * first FRMPayload byte stays clear (the reference's frame has no FPort field;
+ * a caller who sends one puts it there).  d_status[f], in build's order:
+ * -EINVAL for t.fopts_len > 15 or t.mtype > 7; -ENOKEY for t.key >= nkeys;
+ * -ERANGE for a range over 4080 bytes; else 0.  FOpts, the skipped byte and
+ * everything else in d_src keep their contents. */
+int lphy_hip_lorawan_crypt_tx_ragged(uint8_t* d_src, const lphy_lorawan_tx* d_tx, size_t frames,
+                                     const uint8_t* d_keys, size_t nkeys, unsigned skip,
+                                     int32_t* d_status /* may be NULL */, void* stream);
+
+/* After lphy_hip_lorawan_parse_ragged, on its outputs: deciphers the FRMPayload
+ * of every accepted frame in place.  Frame f, with r = d_parsed[f] and d =
+ * d_desc[f]; its row is the len bytes at d_bytes + d.sym_offset / 2 that the
+ * parse call defines from d.samples, symbol_samples and mode.  d_status[f], in
+ * this order, with nothing of the row read or written for any of them:
+ *   - d.samples >= 2^31: -ERANGE;
+ *   - r.status < 0: that status;
+ *   - r.payload_offset + r.payload_len + 4 > len, or r.payload_offset < 8:
+ *     -EINVAL (a record that did not come from the parse call cannot lead
+ *     outside the frame's slot);
+ *   - the key index d_key_used[f] (NULL: key 0) is 0xFFFFFFFF or >= nkeys:
+ *     -ENOKEY;
+ *   - a range over 4080 bytes: -ERANGE.
+ * Otherwise the bytes payload_offset + skip .. payload_offset + payload_len of
+ * the row are deciphered with r.devaddr, r.fcnt widened with zeros and uplink =
+ * ((r.mhdr >> 5) & 1) == 0, and the status is 0.  The header, FOpts, the
+ * skipped byte, the MIC and other frames' bytes are untouched.  After this call
+ * the MIC a row carries no longer covers the bytes in the buffer: it was
+ * computed over the ciphertext, so parse the rows before, not after. */
+int lphy_hip_lorawan_crypt_rx_ragged(uint8_t* d_bytes, const lphy_ragged_desc* d_desc,
+                                     const lphy_lorawan_frame* d_parsed,
+                                     const uint32_t* d_key_used /* may be NULL: key 0 */, size_t frames,
+                                     size_t symbol_samples, int mode, const uint8_t* d_keys, size_t nkeys,
+                                     unsigned skip, int32_t* d_status /* may be NULL */, void* stream);
+
+/* One range through the batch kernel, host buffer in place (device `device`);
+ * serialised process-wide with lphy_hip_lorawan_mic_host.  Returns 0, -EINVAL,
+ * -ERANGE (len > 4080), -ENODEV or -EIO. */
+int lphy_hip_lorawan_crypt_host(int device, const uint8_t key[16], int uplink, uint32_t devaddr, uint32_t fcnt,
+                                uint8_t* data, size_t len);
 
 #ifdef __cplusplus
 }

@@ -24,6 +24,12 @@
 // what lphy_hip_demod_ragged left, with the key found by DevAddr in a sorted
 // session table (k_lw_parse_ragged).  The TU knows no context: the samples of
 // a symbol are an argument.
+//
+// And the FRMPayload cipher of LoRaWAN 1.0.x 4.3.3, which the reference does
+// not have (k_lw_crypt): a keystream of independent AES blocks XORed over byte
+// ranges in place, in front of k_lw_build and behind k_lw_parse_ragged on the
+// same table, or on plain descriptors.  Here the parallelism is across 16-byte
+// blocks as well as across ranges: a group of lanes shares a range.
 #include <hip/hip_runtime.h>
 
 #include <cerrno>
@@ -462,12 +468,150 @@ __global__ void __launch_bounds__(kThreads) k_lw_parse_ragged(
     }
 }
 
+// ---------------------------------------------------- FRMPayload cipher
+// The n (1..16) low bytes of w to p.  A range's neighbours are written by other
+// lanes at the same time, so nothing is read and written back: the bytes in
+// front of the first aligned dword and behind the last whole one go out as
+// bytes, the aligned dwords the block fills as dwords.
+__device__ __forceinline__ void store16(uint8_t* p, unsigned n, const uint32_t w[4]) {
+    const unsigned lead = (unsigned)(-reinterpret_cast<uintptr_t>(p)) & 3;
+    const unsigned head = lead < n ? lead : n;
+    const unsigned whole = (n - head) >> 2, tail = (n - head) & 3;
+#pragma unroll
+    for (unsigned i = 0; i < 3; ++i)
+        if (i < head) p[i] = (uint8_t)byte_of(w[0], i);
+    uint32_t* q = reinterpret_cast<uint32_t*>(p + head);
+    const uint32_t e[5] = {w[0], w[1], w[2], w[3], 0};
+    uint32_t last = 0;  // the bytes behind the whole dwords
+#pragma unroll
+    for (unsigned k = 0; k < 4; ++k) {
+        const uint32_t v = __builtin_amdgcn_alignbit(e[k + 1], e[k], 8 * head);
+        if (k < whole) q[k] = v;
+        if (k == whole) last = v;
+    }
+    uint8_t* t = reinterpret_cast<uint8_t*>(q + whole);
+#pragma unroll
+    for (unsigned i = 0; i < 3; ++i)
+        if (i < tail) t[i] = (uint8_t)byte_of(last, i);
+}
+
+// The three forms of the cipher resolve record f to a job
+// (lphy_lorawan_ragged.h); every lane of a group resolves the same one.
+struct CryptBatch {
+    const lphy_lorawan_desc* desc;
+    __device__ LwCryptJob operator()(unsigned long long f, unsigned long long nkeys) const {
+        return lw_crypt_job_batch(desc[f], nkeys);
+    }
+};
+
+struct CryptTx {
+    const lphy_lorawan_tx* tx;
+    unsigned skip;
+    __device__ LwCryptJob operator()(unsigned long long f, unsigned long long nkeys) const {
+        return lw_crypt_job_tx(tx[f], nkeys, skip);
+    }
+};
+
+struct CryptRx {
+    const lphy_ragged_desc* desc;
+    const lphy_lorawan_frame* parsed;
+    const uint32_t* key_used;
+    unsigned long long step;
+    int mode;
+    unsigned skip;
+    __device__ LwCryptJob operator()(unsigned long long f, unsigned long long nkeys) const {
+        return lw_crypt_job_rx(desc[f], parsed[f], key_used ? key_used[f] : 0u, step, mode, nkeys, skip);
+    }
+};
+
+// Lanes of a job: lane g of the group makes keystream blocks g + 1, g + 1 + G, ...
+// G = 2 by measurement (tools/lorawan_crypt_bench.py): every lane
+// with a block pays a key expansion, about one more block's worth of dependent
+// table reads, so wider groups lose on the 1..16 blocks LoRaWAN payloads have.
+#ifndef LPHY_LW_CRYPT_G
+#define LPHY_LW_CRYPT_G 2
+#endif
+constexpr unsigned kCryptG = LPHY_LW_CRYPT_G;
+static_assert(kCryptG >= 1 && kCryptG <= 32 && (kCryptG & (kCryptG - 1)) == 0, "a power of two dividing 32");
+
+// k_lw_crypt: the keystream blocks of a range are independent, so G
+// consecutive lanes share a job and each lane that has a block expands the key
+// for itself.  The table replica is still threadIdx.x & 31: 32 different banks
+// per ds_read_b32 group whatever G is.
+template <class Front>
+__global__ void __launch_bounds__(kThreads) k_lw_crypt(uint8_t* bytes, Front front, unsigned long long jobs,
+                                                       const uint8_t* keys, unsigned long long nkeys,
+                                                       int32_t* status) {
+    extern __shared__ uint32_t lds[];
+    build_table(lds);
+    const Tab tb = lane_tab(lds);
+    constexpr unsigned per = kThreads / kCryptG;  // jobs of a workgroup per trip
+    const unsigned g = threadIdx.x % kCryptG;
+    for (unsigned long long f = (unsigned long long)blockIdx.x * per + threadIdx.x / kCryptG; f < jobs;
+         f += (unsigned long long)gridDim.x * per) {
+        const LwCryptJob job = front(f, nkeys);
+        if (status && g == 0) status[f] = job.status;
+        const uint32_t nblk = job.status ? 0u : (job.len + 15) / 16;
+        if (g >= nblk) continue;
+        uint32_t k[4], rk[44];
+        load_key(keys, job.key, k);
+        expand_key(tb, k, rk);
+        uint8_t* data = bytes + job.offset;
+        for (uint32_t b = g; b < nblk; b += kCryptG) {
+            const uint32_t have = job.len - 16 * b < 16 ? job.len - 16 * b : 16;
+            uint32_t s[4], w[4];
+            lw_crypt_block(job.uplink, job.devaddr, job.fcnt, b + 1, s);
+            load16(data + 16 * b, have, w);  // in flight during the rounds
+            encrypt(tb, rk, s);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) w[j] ^= s[j];
+            store16(data + 16 * b, have, w);
+        }
+    }
+}
+
 unsigned grid_for(unsigned long long frames) {
     const unsigned long long b = (frames + kThreads - 1) / kThreads;
     return (unsigned)(b < kMaxBlocks ? b : kMaxBlocks);
 }
 
 constexpr size_t kLds = 256 * kCopies * sizeof(uint32_t);  // 32 KiB
+
+// One launch of k_lw_crypt for `jobs` records (0 < jobs < 2^31) of a front end.
+template <class Front>
+int launch_crypt(uint8_t* bytes, Front front, size_t jobs, const uint8_t* keys, size_t nkeys, int32_t* status,
+                 void* stream) {
+    hipLaunchKernelGGL(k_lw_crypt<Front>, dim3(grid_for((unsigned long long)jobs * kCryptG)), dim3(kThreads), kLds,
+                       (hipStream_t)stream, bytes, front, (unsigned long long)jobs, keys, (unsigned long long)nkeys,
+                       status);
+    LW_OK(hipGetLastError());
+    return 0;
+}
+
+// The staging buffer of the host forms on `device`, at least `need` bytes; the
+// device made current.  The caller holds g_stage_mu, which serialises them.
+std::mutex g_stage_mu;
+
+int host_stage(int device, size_t need, uint8_t** base) {
+    struct Stage {
+        void* p = nullptr;
+        size_t bytes = 0;
+    };
+    static std::map<int, Stage> stages;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return -ENODEV;
+    LW_OK(hipSetDevice(device));
+    Stage& s = stages[device];
+    if (s.bytes < need) {
+        if (s.p) (void)hipFree(s.p);
+        s.p = nullptr;
+        s.bytes = 0;
+        LW_OK(hipMalloc(&s.p, need < 4096 ? 4096 : need));
+        s.bytes = need < 4096 ? 4096 : need;
+    }
+    *base = static_cast<uint8_t*>(s.p);
+    return 0;
+}
 
 }  // namespace
 
@@ -541,30 +685,45 @@ int lphy_hip_lorawan_sessions_check(const lphy_lorawan_session* h_sessions, size
     return lw_sessions_check(h_sessions, n);
 }
 
+int lphy_hip_lorawan_crypt_batch(uint8_t* d_bytes, const lphy_lorawan_desc* d_desc, size_t jobs,
+                                 const uint8_t* d_keys, size_t nkeys, int32_t* d_status, void* stream) {
+    if (!jobs) return 0;
+    if (!d_bytes || !d_desc || !d_keys || !nkeys) return -EINVAL;
+    if (reinterpret_cast<uintptr_t>(d_keys) & 15 || reinterpret_cast<uintptr_t>(d_desc) & 15) return -EINVAL;
+    if (jobs > 0x7fffffffULL) return -ERANGE;
+    return launch_crypt(d_bytes, CryptBatch{d_desc}, jobs, d_keys, nkeys, d_status, stream);
+}
+
+int lphy_hip_lorawan_crypt_tx_ragged(uint8_t* d_src, const lphy_lorawan_tx* d_tx, size_t frames,
+                                     const uint8_t* d_keys, size_t nkeys, unsigned skip, int32_t* d_status,
+                                     void* stream) {
+    if (!frames) return 0;
+    if (!d_src || !d_tx || !d_keys || !nkeys || skip > 1) return -EINVAL;
+    if (reinterpret_cast<uintptr_t>(d_keys) & 15 || reinterpret_cast<uintptr_t>(d_tx) & 15) return -EINVAL;
+    if (frames > 0x7fffffffULL) return -ERANGE;
+    return launch_crypt(d_src, CryptTx{d_tx, skip}, frames, d_keys, nkeys, d_status, stream);
+}
+
+int lphy_hip_lorawan_crypt_rx_ragged(uint8_t* d_bytes, const lphy_ragged_desc* d_desc,
+                                     const lphy_lorawan_frame* d_parsed, const uint32_t* d_key_used, size_t frames,
+                                     size_t symbol_samples, int mode, const uint8_t* d_keys, size_t nkeys,
+                                     unsigned skip, int32_t* d_status, void* stream) {
+    if (!frames) return 0;
+    if (!d_bytes || !d_desc || !d_parsed || !d_keys || !nkeys || !symbol_samples || skip > 1) return -EINVAL;
+    if (mode < 0 || mode > 2) return -EINVAL;
+    if (reinterpret_cast<uintptr_t>(d_keys) & 15 || reinterpret_cast<uintptr_t>(d_parsed) & 15) return -EINVAL;
+    if (frames > 0x7fffffffULL) return -ERANGE;
+    return launch_crypt(d_bytes, CryptRx{d_desc, d_parsed, d_key_used, (unsigned long long)symbol_samples, mode, skip},
+                        frames, d_keys, nkeys, d_status, stream);
+}
+
 int lphy_hip_lorawan_mic_host(int device, const uint8_t key[16], int uplink, uint32_t devaddr, uint32_t fcnt,
                               const uint8_t* data, size_t len, uint32_t* mic) {
     if (!key || !mic || (len && !data) || len > 0xFFFFFFFFull - 64) return -EINVAL;
-    struct Stage {
-        void* p = nullptr;
-        size_t bytes = 0;
-    };
-    static std::mutex mu;
-    static std::map<int, Stage> stages;
-    std::lock_guard<std::mutex> lk(mu);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return -ENODEV;
-    LW_OK(hipSetDevice(device));
+    std::lock_guard<std::mutex> lk(g_stage_mu);
     // [key 16 | desc 32 | mic 4 .. pad to 64 | data]
-    const size_t need = 64 + len + 4;
-    Stage& s = stages[device];
-    if (s.bytes < need) {
-        if (s.p) (void)hipFree(s.p);
-        s.p = nullptr;
-        s.bytes = 0;
-        LW_OK(hipMalloc(&s.p, need < 4096 ? 4096 : need));
-        s.bytes = need < 4096 ? 4096 : need;
-    }
-    uint8_t* base = static_cast<uint8_t*>(s.p);
+    uint8_t* base = nullptr;
+    if (int rc = host_stage(device, 64 + len + 4, &base)) return rc;
     lphy_lorawan_desc d{};
     d.offset = 64;
     d.len = (uint32_t)len;
@@ -580,6 +739,36 @@ int lphy_hip_lorawan_mic_host(int device, const uint8_t key[16], int uplink, uin
     if (rc) return rc;
     LW_OK(hipDeviceSynchronize());
     LW_OK(hipMemcpy(mic, base + 48, 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int lphy_hip_lorawan_crypt_host(int device, const uint8_t key[16], int uplink, uint32_t devaddr, uint32_t fcnt,
+                                uint8_t* data, size_t len) {
+    if (!key || (len && !data)) return -EINVAL;
+    if (len > kLwCryptMaxLen) return -ERANGE;
+    std::lock_guard<std::mutex> lk(g_stage_mu);
+    // [key 16 | desc 32 | status 4 .. pad to 64 | data]
+    uint8_t* base = nullptr;
+    if (int rc = host_stage(device, 64 + len + 4, &base)) return rc;
+    if (!len) return 0;
+    lphy_lorawan_desc d{};
+    d.offset = 64;
+    d.len = (uint32_t)len;
+    d.devaddr = devaddr;
+    d.fcnt = fcnt;
+    d.key = 0;
+    d.uplink = uplink ? 1u : 0u;
+    LW_OK(hipMemcpy(base, key, 16, hipMemcpyHostToDevice));
+    LW_OK(hipMemcpy(base + 16, &d, sizeof d, hipMemcpyHostToDevice));
+    LW_OK(hipMemcpy(base + 64, data, len, hipMemcpyHostToDevice));
+    const int rc = lphy_hip_lorawan_crypt_batch(base, reinterpret_cast<const lphy_lorawan_desc*>(base + 16), 1, base,
+                                                1, reinterpret_cast<int32_t*>(base + 48), nullptr);
+    if (rc) return rc;
+    LW_OK(hipDeviceSynchronize());
+    int32_t st = 0;
+    LW_OK(hipMemcpy(&st, base + 48, 4, hipMemcpyDeviceToHost));
+    if (st) return st;
+    LW_OK(hipMemcpy(data, base + 64, len, hipMemcpyDeviceToHost));
     return 0;
 }
 

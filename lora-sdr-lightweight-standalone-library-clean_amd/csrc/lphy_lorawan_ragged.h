@@ -1,11 +1,13 @@
 // lphy_lorawan_ragged.h — what the LoRaWAN calls on a ragged table
 // (lphy_hip_lorawan_build_ragged, lphy_hip_lorawan_parse_ragged) share between
 // the kernels of lphy_lorawan.hip and the host: the frame geometry, the
-// lower-bound search of the session table, encodeHamming84sx of a byte, and
-// the two host-only helpers (lphy_hip_lorawan_tx_layout,
-// lphy_hip_lorawan_sessions_check).  Plain C++ with LPHY_LW_HD in front of what
-// the kernels call too, so the CPU tests compile it alone
-// (tests/cpp/lorawan_ragged_check.cpp).
+// lower-bound search of the session table, encodeHamming84sx of a byte, the
+// payload cipher's A_i block and the front ends that resolve a record to a
+// cipher job (lphy_hip_lorawan_crypt_*), and the two host-only helpers
+// (lphy_hip_lorawan_tx_layout, lphy_hip_lorawan_sessions_check).  Plain C++
+// with LPHY_LW_HD in front of what the kernels call too, so the CPU tests
+// compile it alone (tests/cpp/lorawan_ragged_check.cpp,
+// tests/cpp/lorawan_crypt_check.cpp).
 #pragma once
 #include <cerrno>
 #include <cstddef>
@@ -57,6 +59,64 @@ LPHY_LW_HD constexpr uint32_t lw_enc84(uint32_t x) {
            (((x ^ x >> 1 ^ x >> 3) & 1) << 6) | (((x ^ x >> 2 ^ x >> 3) & 1) << 7);
 }
 LPHY_LW_HD constexpr uint32_t lw_encode_byte(uint32_t b) { return lw_enc84((b >> 4) & 0xF) | lw_enc84(b & 0xF) << 16; }
+
+// ------------------------------------------------- FRMPayload cipher
+// LoRaWAN 1.0.x 4.3.3: the range is XORed with S_1 | S_2 | ..., S_i =
+// AES128(K, A_i).  i is one byte, so a range has at most 255 blocks.
+constexpr uint32_t kLwCryptMaxLen = 255u * 16u;
+
+// A_i as four little-endian words (bytes 4j .. 4j + 3 in word j): B0 of
+// compute_mic (lorawan.cpp:46-58) with 0x49 -> 0x01 and byte 15 = i
+LPHY_LW_HD inline void lw_crypt_block(bool uplink, uint32_t devaddr, uint32_t fcnt, uint32_t i, uint32_t a[4]) {
+    a[0] = 0x01u;
+    a[1] = (uplink ? 0u : 1u) << 8 | (devaddr & 0xFFFFu) << 16;
+    a[2] = devaddr >> 16 | (fcnt & 0xFFFFu) << 16;
+    a[3] = fcnt >> 16 | (i & 0xFFu) << 24;
+}
+
+// What a front end of the cipher kernel resolves a record to: `len` bytes at
+// byte `offset` of the buffer, or a status that refuses the job.
+struct LwCryptJob {
+    uint64_t offset;
+    uint32_t len, devaddr, fcnt, key;
+    bool uplink;
+    int32_t status;
+};
+
+LPHY_LW_HD inline LwCryptJob lw_crypt_refuse(int32_t status) { return LwCryptJob{0, 0, 0, 0, 0, false, status}; }
+
+// lphy_hip_lorawan_crypt_batch
+LPHY_LW_HD inline LwCryptJob lw_crypt_job_batch(const lphy_lorawan_desc& d, uint64_t nkeys) {
+    if (d.key >= nkeys) return lw_crypt_refuse(-ENOKEY);
+    if (d.len > kLwCryptMaxLen) return lw_crypt_refuse(-ERANGE);
+    return LwCryptJob{d.offset, d.len, d.devaddr, d.fcnt, d.key, d.uplink != 0, 0};
+}
+
+// lphy_hip_lorawan_crypt_tx_ragged: FRMPayload behind FOpts at src_offset,
+// the checks in lphy_hip_lorawan_build_ragged's order
+LPHY_LW_HD inline LwCryptJob lw_crypt_job_tx(const lphy_lorawan_tx& t, uint64_t nkeys, uint32_t skip) {
+    if (t.fopts_len > 15 || t.mtype > 7) return lw_crypt_refuse(-EINVAL);
+    if (t.key >= nkeys) return lw_crypt_refuse(-ENOKEY);
+    const uint32_t len = t.payload_len > skip ? t.payload_len - skip : 0;
+    if (len > kLwCryptMaxLen) return lw_crypt_refuse(-ERANGE);
+    return LwCryptJob{t.src_offset + t.fopts_len + skip, len, t.devaddr, t.fcnt, t.key, (t.mtype & 1) == 0, 0};
+}
+
+// lphy_hip_lorawan_crypt_rx_ragged: FRMPayload of the row
+// lphy_hip_lorawan_parse_ragged parsed (the same row length), `key` what
+// d_key_used holds for the frame (0 without it)
+LPHY_LW_HD inline LwCryptJob lw_crypt_job_rx(const lphy_ragged_desc& d, const lphy_lorawan_frame& r, uint32_t key,
+                                             uint64_t step, int mode, uint64_t nkeys, uint32_t skip) {
+    if (d.samples >= kRaggedMaxSamples) return lw_crypt_refuse(-ERANGE);
+    if (r.status < 0) return lw_crypt_refuse(r.status);
+    const uint64_t row = ragged_out_syms(d.samples / step, mode) / 2;
+    if (uint64_t(r.payload_offset) + r.payload_len + 4 > row || r.payload_offset < 8) return lw_crypt_refuse(-EINVAL);
+    if (key == kLwNoKey || key >= nkeys) return lw_crypt_refuse(-ENOKEY);
+    const uint32_t len = r.payload_len > skip ? r.payload_len - skip : 0;
+    if (len > kLwCryptMaxLen) return lw_crypt_refuse(-ERANGE);
+    return LwCryptJob{d.sym_offset / 2 + r.payload_offset + skip, len, r.devaddr, r.fcnt, key,
+                      ((r.mhdr >> 5) & 1) == 0, 0};
+}
 
 // lphy_hip_lorawan_sessions_check
 inline int lw_sessions_check(const lphy_lorawan_session* s, size_t n) {

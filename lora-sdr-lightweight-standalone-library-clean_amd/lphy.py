@@ -117,6 +117,8 @@ EXPORTS = (
     "lphy_hip_detect_ragged", "lphy_hip_detect_ragged_host",
     "lphy_hip_symbol_samples", "lphy_hip_lorawan_build_ragged", "lphy_hip_lorawan_tx_layout",
     "lphy_hip_lorawan_parse_ragged", "lphy_hip_lorawan_sessions_check",
+    "lphy_hip_lorawan_crypt_batch", "lphy_hip_lorawan_crypt_tx_ragged", "lphy_hip_lorawan_crypt_rx_ragged",
+    "lphy_hip_lorawan_crypt_host",
 )
 
 WHITEN_SX1232, WHITEN_SX1272, WHITEN_SX1272_LFSR = 0, 1, 2
@@ -219,6 +221,11 @@ def load(path: Path | None = None) -> C.CDLL:
     L.lphy_hip_lorawan_parse_ragged.argtypes = [_vp, _vp, _sz, _sz, C.c_int, _vp, _vp, _sz, _vp, _vp, _sz, _vp,
                                                 _vp, _vp]
     L.lphy_hip_lorawan_sessions_check.argtypes = [_vp, _sz]
+    L.lphy_hip_lorawan_crypt_batch.argtypes = [_vp, _vp, _sz, _vp, _sz, _vp, _vp]
+    L.lphy_hip_lorawan_crypt_tx_ragged.argtypes = [_vp, _vp, _sz, _vp, _sz, C.c_uint, _vp, _vp]
+    L.lphy_hip_lorawan_crypt_rx_ragged.argtypes = [_vp, _vp, _vp, _vp, _sz, _sz, C.c_int, _vp, _sz, C.c_uint, _vp,
+                                                   _vp]
+    L.lphy_hip_lorawan_crypt_host.argtypes = [C.c_int, _vp, C.c_int, C.c_uint32, C.c_uint32, _vp, _sz]
     _LIBS[str(path)] = L
     return L
 
@@ -960,3 +967,62 @@ def lorawan_mic(key, uplink, devaddr, fcnt, data, device=0):
                                           fcnt & 0xFFFFFFFF, d.ctypes.data, len(data), C.byref(out)),
          "lphy_hip_lorawan_mic_host")
     return out.value
+
+
+# --- the FRMPayload cipher (LoRaWAN 1.0.x 4.3.3; include/lphy_hip.h) -------
+LW_CRYPT_MAX = 4080  # bytes of one range: 255 keystream blocks
+
+
+def lorawan_crypt_batch(data, desc, keys, status=None, stream=None):
+    """The payload cipher in place on the range of every descriptor row
+    (lphy_hip_lorawan_crypt_batch).  data: uint8 device tensor; desc: device
+    tensor holding LORAWAN_DESC_DTYPE records (bytes); keys: uint8 device tensor
+    of 16-byte keys; status (optional): int32 per job, 0 or a negative errno.
+    Asynchronous."""
+    jobs = desc.numel() * desc.element_size() // 32
+    nkeys = keys.numel() // 16
+    ps = _dptr(status, "status", jobs * 4, 4) if status is not None else None
+    _chk(load().lphy_hip_lorawan_crypt_batch(_dptr(data, "data", 1, 1), _dptr(desc, "desc", jobs * 32), jobs,
+                                             _dptr(keys, "keys", nkeys * 16, 1), nkeys, ps, stream),
+         "lphy_hip_lorawan_crypt_batch")
+
+
+def lorawan_crypt_tx_ragged(src, tx, frames, keys, skip=0, status=None, stream=None, src_bytes=None):
+    """The payload cipher on the FRMPayload of every frame of `tx`, in place in
+    `src`, before lorawan_build_ragged reads it (lphy_hip_lorawan_crypt_tx_ragged).
+    src, tx, src_bytes as for lorawan_build_ragged; keys: the payload keys,
+    indexed like build's; skip: 1 leaves the first FRMPayload byte clear;
+    status (optional): int32 per frame.  Asynchronous."""
+    nkeys = keys.numel() // 16
+    ps = _dptr(status, "status", frames * 4, 4) if status is not None else None
+    _chk(load().lphy_hip_lorawan_crypt_tx_ragged(
+        _dptr(src, "src", src_bytes or 0, 1), _dptr(tx, "tx", frames * 32), frames,
+        _dptr(keys, "keys", nkeys * 16, 1), nkeys, skip, ps, stream), "lphy_hip_lorawan_crypt_tx_ragged")
+
+
+def lorawan_crypt_rx_ragged(data, desc, parsed, frames, symbol_samples, mode, keys, key_used=None, skip=0,
+                            status=None, stream=None, out_syms=None):
+    """The payload cipher on the FRMPayload of every frame lorawan_parse_ragged
+    accepted, in place in `data` (lphy_hip_lorawan_crypt_rx_ragged).  data,
+    desc, symbol_samples, mode, out_syms as for lorawan_parse_ragged; parsed:
+    its `out`; key_used (optional): its key_used, int32 per frame (absent: key
+    0); keys: the payload keys, indexed like parse's; status (optional): int32
+    per frame.  The MICs in `data` no longer cover it afterwards.  Asynchronous."""
+    nkeys = keys.numel() // 16
+    pu = _dptr(key_used, "key_used", frames * 4, 4) if key_used is not None else None
+    ps = _dptr(status, "status", frames * 4, 4) if status is not None else None
+    _chk(load().lphy_hip_lorawan_crypt_rx_ragged(
+        _dptr(data, "data", ((out_syms or 0) + 1) // 2, 1), _dptr(desc, "desc", (frames + 1) * 32),
+        _dptr(parsed, "parsed", frames * 32), pu, frames, symbol_samples, mode,
+        _dptr(keys, "keys", nkeys * 16, 1), nkeys, skip, ps, stream), "lphy_hip_lorawan_crypt_rx_ragged")
+
+
+def lorawan_crypt(key, uplink, devaddr, fcnt, data, device=0) -> bytes:
+    """The payload cipher on host bytes, once through the GPU: ciphertext of a
+    plaintext and the other way round."""
+    k = np.frombuffer(bytes(key), np.uint8)
+    d = np.frombuffer(bytes(data) + b"\0", np.uint8).copy()
+    _chk(load().lphy_hip_lorawan_crypt_host(device, k.ctypes.data, int(uplink), devaddr & 0xFFFFFFFF,
+                                            fcnt & 0xFFFFFFFF, d.ctypes.data, len(data)),
+         "lphy_hip_lorawan_crypt_host")
+    return d[:len(data)].tobytes()
