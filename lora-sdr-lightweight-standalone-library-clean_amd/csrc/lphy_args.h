@@ -2,12 +2,16 @@
 // no device code of its own: the kernels' argument structs, the per-SF launch
 // tables (SfOps, filled by each lphy_sf.hip object, read by lphy_hip.hip),
 // the frame status codes that pass between the launches of one call, the
-// MODE template bits and HIP_OK.
+// MODE template bits, HIP_OK, and the one answer to "how many workgroups of
+// kernel K does this device hold at once" (resident_blocks, per device) with
+// the one clamp of a persistent grid to it (persistent_grid).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cerrno>
 #include <cstdio>
+#include <mutex>
+#include <vector>
 
 #include "../../include/lphy_hip.h"
 #include "lphy_fft.h"  // cf32, kTile
@@ -72,31 +76,32 @@ struct RaggedArgs {
     int decode;
 };
 
-// lphy_hip_detect_batch (lphy_detect.h): window w feeds the detector the N
-// samples iq[first + w * hop + i * step]
+// The detector (lphy_detect.h): what both of its forms share ...
 struct DetectArgs {
-    const cf32* iq;        // total_samples
+    const cf32* iq;
     const cf32* tw;        // N twiddles (KISS, forward)
     const cf32* down;      // N down-chirp samples
     const float* win;      // N window coefficients or nullptr
-    lphy_detect_rec* out;  // windows records
-    unsigned long long total_samples;
-    unsigned long long first, hop, step, windows;
-    int dechirp;           // LPHY_DET_DECHIRP
+    lphy_detect_rec* out;  // one record per unit
+    int dechirp;           // LPHY_DET_DECHIRP (the launcher reads it)
     float power_scale;     // LoRaDetector.hpp:29
     unsigned long long* counters;  // ctx counters (kCtrDetectSerial)
 };
 
-// lphy_hip_detect_ragged (lphy_detect.h): symbol s of frame f feeds the
-// detector iq[desc[f].iq_offset + s * N * osr + phase + i * osr], record
-// out[desc[f].unit_offset + s].  Of D it reads the tables, iq, out,
-// power_scale and counters (and the launcher dechirp).
-struct DetectRaggedArgs {
-    DetectArgs D;
+// ... and the window geometry of each.  lphy_hip_detect_batch: window w feeds
+// the detector the N samples iq[first + w * hop + i * step], record out[w]
+struct DetLattice {
+    unsigned long long first, hop, step, windows, total_samples;
+};
+
+// lphy_hip_detect_ragged: symbol s of frame f feeds the detector
+// iq[desc[f].iq_offset + s * N * osr + phase + i * osr], record
+// out[desc[f].unit_offset + s]
+struct DetRagged {
     const lphy_ragged_desc* desc;  // frames + 1 records
     unsigned frames;               // < 2^31
     unsigned osr, phase;           // phase < osr
-    unsigned long long units_hint; // whole symbols of the call when the host knows them, else 0
+    unsigned long long units_hint; // as RaggedArgs' (the launcher reads it)
 };
 
 // Per-SF launch entry points (one table per lphy_sf.hip instance)
@@ -112,13 +117,13 @@ struct SfOps {
     // grid_cap > 0 caps the symbol kernel's persistent grid (test build:
     // lphy_hip_test_grid_cap, else 0)
     int (*ragged)(const RaggedArgs&, hipStream_t, unsigned grid_cap);
-    // lphy_hip_detect_batch: k_detect (SF 7-12); grid_cap as above
-    int (*detect)(const DetectArgs&, hipStream_t, unsigned grid_cap);
+    // lphy_hip_detect_batch: k_detect over the lattice (SF 7-12); grid_cap as above
+    int (*detect)(const DetectArgs&, const DetLattice&, hipStream_t, unsigned grid_cap);
     // lphy_hip_estimate_ragged: k_rg_estimate (SF 7-12); of RaggedArgs it
     // reads A's tables, iq, meta, frames, osr and desc
     int (*estimate_ragged)(const RaggedArgs&, unsigned long long est_samples, hipStream_t);
-    // lphy_hip_detect_ragged: k_detect_ragged (SF 7-12); grid_cap as above
-    int (*detect_ragged)(const DetectRaggedArgs&, hipStream_t, unsigned grid_cap);
+    // lphy_hip_detect_ragged: k_detect over the table (SF 7-12); grid_cap as above
+    int (*detect_ragged)(const DetectArgs&, const DetRagged&, hipStream_t, unsigned grid_cap);
 };
 extern const SfOps sf_ops_1, sf_ops_2, sf_ops_3, sf_ops_4, sf_ops_5, sf_ops_6,
     sf_ops_7, sf_ops_8, sf_ops_9, sf_ops_10, sf_ops_11, sf_ops_12;
@@ -160,6 +165,59 @@ struct FrameArgs {
     DemodArgs A;
     unsigned waves;  // wavefronts in the grid
 };
+
+// query(device) >= 0, asked once per device and call site (Fn: the site's
+// lambda); `other` for a device the runtime does not count.
+template <class Fn>
+long long per_device(int device, long long other, Fn query) {
+    static std::mutex m;
+    static std::vector<long long> v;  // -1: not asked yet
+    std::lock_guard<std::mutex> g(m);
+    if (v.empty()) {
+        int n = 0;
+        (void)hipGetDeviceCount(&n);
+        v.assign(n > 0 ? n : 1, -1);
+    }
+    if (device < 0 || (size_t)device >= v.size()) return other;
+    if (v[device] < 0) v[device] = query(device);
+    return v[device];
+}
+
+// the device this thread launches on (the entry points set the context's)
+inline int current_device() {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    return dev;
+}
+
+// CUs of `device` ...
+inline int device_cus(int device) {
+    return (int)per_device(device, 256, [](int d) {
+        int n = 0;
+        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d);
+        return n > 0 ? n : 256;
+    });
+}
+// ... and the workgroups of kTile threads of kernel K that `device`, the
+// current one, holds at once
+template <auto K>
+int resident_blocks(int device) {
+    return (int)per_device(device, 256, [](int d) {
+        int per = 0;
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, K, kTile, 0);
+        return device_cus(d) * (per > 0 ? per : 1);
+    });
+}
+
+// Workgroups of a persistent grid: the `resident` ones, no more than the
+// call's `tiles` when the host knows them (else 0: the workgroups past the
+// last unit leave at once), no more than `cap` when there is one (else 0).
+inline unsigned persistent_grid(unsigned long long resident, unsigned long long tiles, unsigned long long cap) {
+    unsigned long long grid = resident;
+    if (tiles && grid > tiles) grid = tiles;
+    if (cap && grid > cap) grid = cap;
+    return (unsigned)grid;
+}
 
 }  // namespace
 

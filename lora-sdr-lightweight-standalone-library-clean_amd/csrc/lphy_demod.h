@@ -7,7 +7,7 @@
 // the staging, UnitResult, EstFold, the certificate; and the exact passes of
 // the paths that reproduce the reference's arithmetic plainly (k_maxabs,
 // k_estimate, lphy_post.h, lphy_ragged.h): workgroup_max, estimate_unit,
-// exact_symbol, settle_verdict, and the ragged tables' unit_frame.
+// exact_symbol, settle_verdict, and load_tables (the call's tables into LDS).
 #pragma once
 #include "lphy_args.h"
 #include "libm_exact.h"
@@ -36,6 +36,19 @@ __device__ __forceinline__ cf32 est_sample(const DemodArgs& A, const cf32* fr,
     if (A.mode != LPHY_MODE_DEMODULATE && m.normalised) x = cscale(x, m.scale);
     if (A.win) x = cscale(x, A.win[i]);
     return x;
+}
+
+// The call's N twiddles (A.tw) and, where the kernel keeps them in LDS, its
+// down-chirp (DOWN: A.down) and window (WIN: A.win) into the workgroup's
+// arrays, by all kTile threads.  No barrier: the caller's next one publishes
+// them.
+template <int N, bool DOWN, bool WIN, class ARGS>
+__device__ __forceinline__ void load_tables(const ARGS& A, cf32* twl, cf32* dnl = nullptr, float* wnl = nullptr) {
+    for (int i = threadIdx.x; i < N; i += kTile) {
+        twl[i] = A.tw[i];
+        if constexpr (DOWN) dnl[i] = A.down[i];
+        if constexpr (WIN) wnl[i] = A.win[i];
+    }
 }
 
 // max(|I|,|Q|) accumulation of LoRaDemod.cpp:62-66 for one sample:
@@ -648,20 +661,6 @@ __device__ __forceinline__ lphy_frame_meta settle_verdict(const lphy_frame_meta&
     e.sw1 = sm.sw1;
     e.status = !ok ? kStatusFixup : (open ? kStatusRecheck : 0);
     return e;
-}
-
-// Frame of unit u in a ragged table (lphy_ragged_desc, frames + 1 records):
-// the last record whose unit_offset is <= u, for u below the table's total.
-__device__ __forceinline__ unsigned unit_frame(const lphy_ragged_desc* __restrict__ desc, unsigned nframes,
-                                               unsigned long long u) {
-    // unit_offset[lo] <= u < unit_offset[hi] throughout
-    unsigned lo = 0, hi = nframes;
-    while (hi - lo > 1) {
-        const unsigned mid = lo + ((hi - lo) >> 1);
-        if (desc[mid].unit_offset <= u) lo = mid;
-        else hi = mid;
-    }
-    return lo;
 }
 
 // Stage 2: per-symbol demodulation, persistent grid.  The workgroup stages

@@ -1,8 +1,8 @@
 // lphy_detect.h — lphy_hip_detect_batch: LoRaDetector<float>::detect
 // (LoRaDetector.hpp:39-74) over a batch of windows, all four outputs per
 // window (lphy_detect_rec, include/lphy_hip.h).  One launch, k_detect<SF,
-// PREP>: a persistent grid over tiles of T windows, one team (the LPS lanes
-// of one symbol) per window as in k_rg_demod.  Window w feeds the detector
+// PREP, DetLattice>: a persistent grid over tiles of T windows, one team (the
+// LPS lanes of one symbol) per window as in k_rg_demod.  Window w feeds it
 // the N samples iq[first + w * hop + i * step], prepared per PREP:
 // [x down[i] with the reference's complex product] [x win[i]].
 //   stage (Stage<SF>) -> exact KISS transform with the Annex G products
@@ -38,12 +38,13 @@
 // in the context's kCtrDetectSerial (lphy_hip_detect_serial_count).
 //
 // lphy_hip_detect_ragged is the same detector on every whole symbol of every
-// frame of a lphy_ragged_desc table: k_detect_ragged<SF, PREP> finds each
-// team's window from the table (unit_frame, as k_rg_demod) instead of the
-// lattice.  What follows per window is one function, detect_window, which both
-// kernels call.
+// frame of a lphy_ragged_desc table, and the same kernel: k_detect<SF, PREP,
+// GEO> takes the window geometry, DetLattice or DetRagged (once a kernel of
+// its own, k_detect_ragged), whose det_unit finds each team's window.  What
+// follows per window is one function, detect_window.
 #pragma once
 #include "lphy_demod.h"
+#include "lphy_ragged_unit.h"
 
 namespace {
 
@@ -67,10 +68,10 @@ __device__ __attribute__((noinline)) float detect_walk(const cf32* lds, int slot
     return (float)(total - (double)max_value);
 }
 
-// One window of one team, all four outputs: what k_detect and
-// k_detect_ragged do per tile once each team knows its window.  The team's
-// window is the N samples iq[base + i * step]; its record goes to out[w].  A
-// team that is not `live` stages zeros and writes nothing.  Every thread of
+// One window of one team, all four outputs: what k_detect does per tile once
+// each team knows its window (det_unit).  The team's window is the N samples
+// iq[base + i * step]; its record goes to out[w].  A team that is not
+// `live` stages zeros and writes nothing.  Every thread of
 // the workgroup calls this together (it holds the tile's barriers; the first
 // one also publishes the tables the caller loaded into twl / down / win).
 // `iq_end` / `out_end`: one past the last sample / record the caller may
@@ -176,51 +177,41 @@ __device__ __forceinline__ void detect_window(const cf32* iq, unsigned long long
     }
 }
 
-// Two waves per SIMD up to SF 10, one above (as k_rg_demod).
-template <int SF, int PREP>
-__global__ __launch_bounds__(kTile, SF <= 10 ? 2 : 1) void k_detect(DetectArgs D) {
-    using G = Geo<SF>;
-    constexpr int N = G::N, T = G::T;
-    constexpr bool DECH = (PREP & kPrepDechirp) != 0, WIN = (PREP & kPrepWindow) != 0;
-    constexpr bool TAB = N <= 1024;  // chirp + window tables in LDS
-    __shared__ cf32 lds[T * G::SSTRIDE];
-    __shared__ cf32 twl[N];
-    __shared__ cf32 dnl[TAB && DECH ? N : 1];
-    __shared__ float wnl[TAB && WIN ? N : 1];
-    __shared__ ArgMax red[kTile / 64];
-    __shared__ double reds[kTile / 64];
-    __shared__ float redn[kTile / 64];
+// The window geometries (lphy_args.h): the units of a call, and unit u's
+// first sample, sample stride, end of its IQ (debug build) and record index.
+struct DetUnit {
+    unsigned long long base, step, iq_end, rec;
+    bool live;
+};
 
-    const int tid = threadIdx.x;
-    for (int i = tid; i < N; i += kTile) {
-        twl[i] = D.tw[i];
-        if constexpr (TAB && DECH) dnl[i] = D.down[i];
-        if constexpr (TAB && WIN) wnl[i] = D.win[i];
-    }
-    const cf32* down = TAB && DECH ? dnl : D.down;
-    const float* win = TAB && WIN ? wnl : D.win;
+__device__ __forceinline__ unsigned long long det_units(const DetLattice& g) { return g.windows; }
+__device__ __forceinline__ unsigned long long det_units(const DetRagged& g) { return g.desc[g.frames].unit_offset; }
 
-    const int slot = tid / G::LPS, lam = tid % G::LPS;
-    const Stage<SF> stg(slot, lam);
-    const unsigned long long stride = (unsigned long long)gridDim.x * T;
-    for (unsigned long long t0 = (unsigned long long)blockIdx.x * T; t0 < D.windows; t0 += stride) {
-        const unsigned long long w = t0 + (unsigned)slot;
-        const bool live = w < D.windows;
-        const unsigned long long base = D.first + (live ? w : 0) * D.hop;
-        detect_window<SF, PREP>(D.iq, base, D.step, D.total_samples, live, D.out, w, D.windows, lds, twl, down, win,
-                                red, reds, redn, stg, slot, lam, D.power_scale, D.counters);
-    }
+// window u of the lattice: iq[first + u * hop + i * step], record out[u]
+template <int SF>
+__device__ __forceinline__ DetUnit det_unit(const DetLattice& g, unsigned long long, unsigned long long u) {
+    const bool live = u < g.windows;
+    return DetUnit{g.first + (live ? u : 0) * g.hop, g.step, g.total_samples, u, live};
 }
 
-// lphy_hip_detect_ragged: the detector on every whole symbol of every frame
-// of a lphy_ragged_desc table.  The work unit is the global symbol index u,
-// as in k_rg_demod: a persistent grid over tiles of T units, the team finds
-// its unit's frame by binary search over unit_offset (unit_frame; from SF 10
-// on wave-uniform values) and symbol s = u - unit_offset of that frame is the
-// window iq[iq_offset + s N osr + phase + i osr], whose record is out[u].
-// The workgroups past the table's last unit leave at once.
-template <int SF, int PREP>
-__global__ __launch_bounds__(kTile, SF <= 10 ? 2 : 1) void k_detect_ragged(DetectRaggedArgs R) {
+// unit u of the table, the global symbol index as in k_rg_demod: symbol s of
+// its frame (ragged_unit; from SF 10 on wave-uniform values) is the window
+// iq[iq_offset + s N osr + phase + i osr], whose record is out[u]
+template <int SF>
+__device__ __forceinline__ DetUnit det_unit(const DetRagged& g, unsigned long long units, unsigned long long u) {
+    const RaggedUnit ru = ragged_unit<Geo<SF>::LPS >= 64>(g.desc, g.frames, units, u);
+    // whole symbols of the frame (samples < 2^31 where it counts)
+    const unsigned n = ((unsigned)ru.d.samples >> SF) / g.osr;
+    const bool live = ru.live && ru.d.samples < 0x80000000ull && ru.s < n;
+    const unsigned long long fstep = (unsigned long long)Geo<SF>::N * g.osr;
+    return DetUnit{ru.d.iq_offset + (live ? ru.s : 0) * fstep + g.phase, g.osr, ru.d.iq_offset + n * fstep,
+                   ru.d.unit_offset + ru.s, live};
+}
+
+// A persistent grid over tiles of T units, one team per unit; the workgroups
+// past the last unit leave at once.  Two waves per SIMD up to SF 10, one above.
+template <int SF, int PREP, class GEO>
+__global__ __launch_bounds__(kTile, SF <= 10 ? 2 : 1) void k_detect(DetectArgs D, GEO geo) {
     using G = Geo<SF>;
     constexpr int N = G::N, T = G::T;
     constexpr bool DECH = (PREP & kPrepDechirp) != 0, WIN = (PREP & kPrepWindow) != 0;
@@ -233,43 +224,21 @@ __global__ __launch_bounds__(kTile, SF <= 10 ? 2 : 1) void k_detect_ragged(Detec
     __shared__ double reds[kTile / 64];
     __shared__ float redn[kTile / 64];
 
-    const unsigned nframes = R.frames;
-    const lphy_ragged_desc* __restrict__ desc = R.desc;
-    const unsigned long long units = desc[nframes].unit_offset;
+    const unsigned long long units = det_units(geo);
     if ((unsigned long long)blockIdx.x * T >= units) return;  // uniform
 
-    const DetectArgs& D = R.D;
-    const int tid = threadIdx.x;
-    for (int i = tid; i < N; i += kTile) {
-        twl[i] = D.tw[i];
-        if constexpr (TAB && DECH) dnl[i] = D.down[i];
-        if constexpr (TAB && WIN) wnl[i] = D.win[i];
-    }
+    load_tables<N, TAB && DECH, TAB && WIN>(D, twl, dnl, wnl);
     const cf32* down = TAB && DECH ? dnl : D.down;
     const float* win = TAB && WIN ? wnl : D.win;
 
-    const unsigned osr = R.osr;
+    const int tid = threadIdx.x;
     const int slot = tid / G::LPS, lam = tid % G::LPS;
     const Stage<SF> stg(slot, lam);
     const unsigned long long stride = (unsigned long long)gridDim.x * T;
     for (unsigned long long t0 = (unsigned long long)blockIdx.x * T; t0 < units; t0 += stride) {
-        unsigned long long u = t0 + (unsigned)slot;
-        if constexpr (G::LPS >= 64) {  // one symbol per wavefront or more: scalar search
-            const unsigned lo32 = __builtin_amdgcn_readfirstlane((unsigned)u);
-            const unsigned hi32 = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-            u = ((unsigned long long)hi32 << 32) | lo32;
-        }
-        bool live = u < units;
-        const lphy_ragged_desc d = desc[live ? unit_frame(desc, nframes, u) : 0u];
-        const unsigned long long s = u - d.unit_offset;
-        // whole symbols of the frame (samples < 2^31 where it counts)
-        const unsigned n = ((unsigned)d.samples >> SF) / osr;
-        // (a table whose prefix is wrong cannot lead outside the frame, and u < units)
-        live = live && d.unit_offset <= u && d.samples < 0x80000000ull && s < n;
-        const unsigned long long fstep = (unsigned long long)N * osr;
-        const unsigned long long base = d.iq_offset + (live ? s : 0) * fstep + R.phase;
-        detect_window<SF, PREP>(D.iq, base, osr, d.iq_offset + n * fstep, live, D.out, u, units, lds, twl, down, win,
-                                red, reds, redn, stg, slot, lam, D.power_scale, D.counters);
+        const DetUnit w = det_unit<SF>(geo, units, t0 + (unsigned)slot);
+        detect_window<SF, PREP>(D.iq, w.base, w.step, w.iq_end, w.live, D.out, w.rec, units, lds, twl, down, win, red,
+                                reds, redn, stg, slot, lam, D.power_scale, D.counters);
     }
 }
 

@@ -261,7 +261,7 @@ void ctx_args(const lphy_hip_ctx* c, ARGS& A) {
     A.counters = c->d_counters;
 }
 
-// Most workgroups the persistent grids of k_rg_demod, k_detect, k_detect_ragged and
+// Most workgroups the persistent grids of k_rg_demod, k_detect (both geometries) and
 // k_tx_samples get on this context (0: no cap; test build only,
 // lphy_hip_test_grid_cap).
 unsigned test_grid_cap(const lphy_hip_ctx* c) {
@@ -625,13 +625,8 @@ int detect_impl(lphy_hip_ctx* c, const float* d_iq, size_t total_samples, size_t
     ctx_args(c, D);
     D.iq = reinterpret_cast<const cf32*>(d_iq);
     D.out = d_out;
-    D.total_samples = total_samples;
-    D.first = first;
-    D.hop = hop;
-    D.step = step;
-    D.windows = windows;
     D.dechirp = (flags & LPHY_DET_DECHIRP) ? 1 : 0;
-    return ops->detect(D, st, test_grid_cap(c));
+    return ops->detect(D, DetLattice{first, hop, step, windows, total_samples}, st, test_grid_cap(c));
 }
 }  // namespace
 
@@ -643,7 +638,7 @@ int lphy_hip_detect_batch(lphy_hip_ctx* c, const float* d_iq, size_t total_sampl
     return detect_impl(c, d_iq, total_samples, first, hop, step, windows, d_out, flags, (hipStream_t)stream);
 }
 
-// ---- the detector on a ragged table (k_detect_ragged, lphy_detect.h) -------
+// ---- the detector on a ragged table (k_detect over DetRagged, lphy_detect.h)
 namespace {
 // The argument checks of both forms, in the header's order (before any device
 // call): 0 to go on, 1 when there is nothing to do, or the error.
@@ -666,17 +661,13 @@ int detect_ragged_impl(lphy_hip_ctx* c, const float* d_iq, const lphy_ragged_des
     const SfOps* ops = sf_ops(c->sf);
     if (!ops || !ops->detect_ragged) return -ENOTSUP;  // (an experiment build without this SF's object)
     HIP_OK(hipSetDevice(c->device));
-    DetectRaggedArgs R{};
-    ctx_args(c, R.D);
-    R.D.iq = reinterpret_cast<const cf32*>(d_iq);
-    R.D.out = d_out;
-    R.D.dechirp = (flags & LPHY_DET_DECHIRP) ? 1 : 0;
-    R.desc = d_desc;
-    R.frames = (unsigned)frames;
-    R.osr = (unsigned)c->osr;
-    R.phase = phase;
-    R.units_hint = units_hint;
-    return ops->detect_ragged(R, st, test_grid_cap(c));
+    DetectArgs D{};
+    ctx_args(c, D);
+    D.iq = reinterpret_cast<const cf32*>(d_iq);
+    D.out = d_out;
+    D.dechirp = (flags & LPHY_DET_DECHIRP) ? 1 : 0;
+    return ops->detect_ragged(D, DetRagged{d_desc, (unsigned)frames, (unsigned)c->osr, phase, units_hint}, st,
+                              test_grid_cap(c));
 }
 }  // namespace
 
@@ -872,43 +863,13 @@ constexpr size_t mod_walk_all_below = 4096;
 #define LPHY_MOD_FAST 1
 #endif
 
-struct ModFastLimits {
-    size_t lds = 0;
-};
-const ModFastLimits& mod_fast_limits(int device);
-
-// Which modulator form a call takes (modulate_impl): 0 the three-kernel or
-// batch forms, 1 k_mod_fast with the f rows in LDS, 2 k_mod_fast's split
-// form with the f rows in the phase buffer (GROWS: k_mod_fast<true, 1>,
-// k_mod_cand, k_mod_fast<true, 3>).
-int mod_form(const lphy_hip_ctx* c, size_t frames, size_t nsyms) {
-    const size_t ns = nsyms + 2, nph = frames * ns;
-    if (!LPHY_MOD_FAST || nph >= mod_walk_all_below || ns > (size_t)kModFastSyms) return 0;
-    const size_t lds = ns * (((size_t)c->N * c->osr + 4) * sizeof(float) + kModFastWin);
-    return lds <= mod_fast_limits(c->device).lds ? 1 : 2;
-}
-
-size_t mod_scratch_bytes(const lphy_hip_ctx* c, size_t frames, size_t nsyms) {
-    const size_t nph = frames * (nsyms + 2);
-    return align_up(nph * sizeof(float)) +
-           (nph < mod_walk_all_below ? align_up(nph * (size_t)c->N * c->osr * sizeof(float)) : 0) +
-           (mod_form(c, frames, nsyms) == 2
-                ? align_up(frames * sizeof(ModFastG)) + align_up(frames * (size_t)kModFastSyms * kModFastWin)
-                : 0);
-}
-
 // k_mod_fast's dynamic LDS limit on the context's device, found once per
 // device: the device's LDS per workgroup less the kernel's static LDS
 // (ModFastShared), and the kernel's attribute raised to it once, outside the
 // per-packet path (the limit was a gfx950 constant, set per call).
-const ModFastLimits& mod_fast_limits(int device) {
-    static ModFastLimits lim[64];
-    static std::once_flag once[64];
-    // (a device past the table: the limit no attribute has to be raised for)
-    static const ModFastLimits unraised{size_t(64) << 10};
-    if (device < 0 || device >= 64) return unraised;
-    const int d = device;
-    std::call_once(once[d], [d] {
+size_t mod_fast_lds(int device) {
+    // (a device the runtime does not count: the limit no attribute has to be raised for)
+    return (size_t)per_device(device, 64 << 10, [](int d) {
         int cur = 0, per_block = 0;
         (void)hipGetDevice(&cur);
         (void)hipSetDevice(d);
@@ -922,10 +883,29 @@ const ModFastLimits& mod_fast_limits(int device) {
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_mod_fast<false>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)avail) != hipSuccess)
             avail = std::min<size_t>(avail, size_t(64) << 10);  // the default limit stands
-        lim[d].lds = avail;
         (void)hipSetDevice(cur);
+        return avail;
     });
-    return lim[d];
+}
+
+// Which modulator form a call takes (modulate_impl): 0 the three-kernel or
+// batch forms, 1 k_mod_fast with the f rows in LDS, 2 k_mod_fast's split
+// form with the f rows in the phase buffer (GROWS: k_mod_fast<true, 1>,
+// k_mod_cand, k_mod_fast<true, 3>).
+int mod_form(const lphy_hip_ctx* c, size_t frames, size_t nsyms) {
+    const size_t ns = nsyms + 2, nph = frames * ns;
+    if (!LPHY_MOD_FAST || nph >= mod_walk_all_below || ns > (size_t)kModFastSyms) return 0;
+    const size_t lds = ns * (((size_t)c->N * c->osr + 4) * sizeof(float) + kModFastWin);
+    return lds <= mod_fast_lds(c->device) ? 1 : 2;
+}
+
+size_t mod_scratch_bytes(const lphy_hip_ctx* c, size_t frames, size_t nsyms) {
+    const size_t nph = frames * (nsyms + 2);
+    return align_up(nph * sizeof(float)) +
+           (nph < mod_walk_all_below ? align_up(nph * (size_t)c->N * c->osr * sizeof(float)) : 0) +
+           (mod_form(c, frames, nsyms) == 2
+                ? align_up(frames * sizeof(ModFastG)) + align_up(frames * (size_t)kModFastSyms * kModFastWin)
+                : 0);
 }
 
 int modulate_impl(lphy_hip_ctx* c, const uint16_t* d_syms, size_t frames, size_t nsyms,
@@ -1062,22 +1042,6 @@ int tx_check(const lphy_hip_ctx* c, const void* src, const void* desc, size_t fr
 }
 
 extern "C++" {
-// k_tx_samples<SRC>'s persistent grid: every workgroup the device holds at
-// once, found once per device (the device form does not know the call's units).
-template <class SRC>
-unsigned tx_resident_grid(int device) {
-    static unsigned grid[64];
-    static std::once_flag once[64];
-    const int d = device >= 0 && device < 64 ? device : 0;
-    std::call_once(once[d], [d, device] {
-        int per = 0, cus = 0;
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_tx_samples<SRC>, kTile, 0);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-        grid[d] = (unsigned)((cus > 0 ? cus : 256) * (per > 0 ? per : 1));
-    });
-    return grid[d];
-}
-
 // The two launches.  units_hint: the call's whole symbols when the caller's
 // table is on the host (the sample pass's grid then stops at its tiles).
 template <class SRC>
@@ -1094,9 +1058,9 @@ int tx_launch(const lphy_hip_ctx* c, SRC src, const lphy_ragged_desc* d_desc, si
     A.bws = (float)c->bw_hz / 125000.0f;
     A.ampl = std::max(-1.0f, std::min(1.0f, amplitude));  // LoRaMod.cpp:18
     A.sync = sync;
-    unsigned grid = tx_resident_grid<SRC>(c->device);
-    if (units_hint) grid = (unsigned)std::min<unsigned long long>(grid, (units_hint + kTile - 1) / kTile);
-    if (const unsigned cap = test_grid_cap(c)) grid = std::min(grid, cap);
+    // (the device form does not know the call's units: units_hint 0)
+    const unsigned grid = persistent_grid(resident_blocks<&k_tx_samples<SRC>>(c->device),
+                                          (units_hint + kTile - 1) / kTile, test_grid_cap(c));
     hipLaunchKernelGGL(k_tx_walk<SRC>, dim3((unsigned)((frames + 63) / 64)), dim3(64), 0, st, A, src);
     hipLaunchKernelGGL(k_tx_samples<SRC>, dim3(grid), dim3(kTile), 0, st, A, src);
     HIP_OK(hipGetLastError());
@@ -1150,7 +1114,7 @@ int lphy_hip_test_pinned_max(lphy_hip_ctx* c, size_t bytes) {
 }
 
 // Test build only: at most `blocks` workgroups in the persistent grids of
-// k_rg_demod, k_detect, k_detect_ragged and k_tx_samples on this context, after the launchers'
+// k_rg_demod, k_detect (both geometries) and k_tx_samples on this context, after the launchers'
 // own caps (0: the default).  A small call then walks its grid-stride loops
 // more than once, which otherwise needs more tiles than the device holds
 // workgroups.

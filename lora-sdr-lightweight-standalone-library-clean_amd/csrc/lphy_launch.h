@@ -3,7 +3,8 @@
 // them a call takes is lphy_route.h's decision (lphy_hip.hip); which kernels
 // exist here follows the same header's frames_kernel / wave_kernel, so a
 // routed call always finds its kernel and the -ENOTSUP returns below only
-// guard a table entry that does not exist.
+// guard a table entry that does not exist.  Every persistent grid here is
+// persistent_grid over resident_blocks<K> / device_cus (lphy_args.h).
 #pragma once
 #include <type_traits>
 
@@ -39,26 +40,16 @@ int with_mode(int mode, bool win, bool osr, Fn&& fn) {
     return with_mode_bits<0>(mode, fn);
 }
 
-// CUs of the device (queried once) ...
-inline int cu_count() {
-    static const int cus = [] {
-        int dev = 0, n = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return n > 0 ? n : 256;
-    }();
-    return cus;
-}
-// ... and the persistent grid of kernel K: every workgroup of kTile threads
-// the device holds at once
-template <auto K>
-int resident_grid() {
-    static const int grid = [] {
-        int per = 0;
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, K, kTile, 0);
-        return cu_count() * (per > 0 ? per : 1);
-    }();
-    return grid;
+// The detector's compile-time PREP of a call (lphy_detect.h).  Calls
+// fn(std::integral_constant<int, PREP>).
+template <class Fn>
+void with_prep(bool dechirp, bool win, Fn&& fn) {
+    switch ((dechirp ? kPrepDechirp : 0) | (win ? kPrepWindow : 0)) {
+        case 0: fn(std::integral_constant<int, 0>{}); break;
+        case kPrepDechirp: fn(std::integral_constant<int, kPrepDechirp>{}); break;
+        case kPrepWindow: fn(std::integral_constant<int, kPrepWindow>{}); break;
+        default: fn(std::integral_constant<int, kPrepDechirp | kPrepWindow>{}); break;
+    }
 }
 
 // Waves per SIMD the demod kernel is register-budgeted for (launch bound):
@@ -73,11 +64,11 @@ void launch_symbols(const DemodArgs& A0, hipStream_t st, int per_cu) {
     constexpr bool WAVE = G::LPS <= 64;
     constexpr int WT = WAVE ? 64 / G::LPS : G::T;      // symbols per worker tile
     constexpr int WPB = WAVE ? kTile / 64 : 1;         // workers per workgroup
-    unsigned long long g = (unsigned long long)resident_grid<&k_demod<SF, MODE, OCC>>();
-    if (per_cu > 0 && g > (unsigned long long)per_cu * cu_count()) g = (unsigned long long)per_cu * cu_count();
+    const int dev = current_device();
     const unsigned long long wtiles = (A0.frames * A0.total_syms + WT - 1) / WT;
-    unsigned long long grid = (wtiles + WPB - 1) / WPB;
-    if (grid > g) grid = g;
+    const unsigned long long grid =
+        persistent_grid(resident_blocks<&k_demod<SF, MODE, OCC>>(dev), (wtiles + WPB - 1) / WPB,
+                        per_cu > 0 ? (unsigned long long)per_cu * device_cus(dev) : 0);
     DemodArgs A = A0;
     const unsigned long long stride = grid * WPB * WT;  // symbols per worker step
     A.stride_f = (unsigned)(stride / A0.total_syms);
@@ -131,11 +122,10 @@ int launch_frames_sf(const DemodArgs& A, hipStream_t st) {
             FrameArgs P{};
             P.A = A;
             constexpr unsigned WPB = kTile / 64;
-            unsigned long long blocks = (unsigned long long)resident_grid<&k_frames<SF, MODE, LPHY_FRAMES_OCC>>();
-            const unsigned long long need = (A.frames + WPB - 1) / WPB;
-            if (blocks > need) blocks = need;
-            P.waves = (unsigned)(blocks * WPB);
-            hipLaunchKernelGGL((k_frames<SF, MODE, LPHY_FRAMES_OCC>), dim3((unsigned)blocks), dim3(kTile), 0, st, P);
+            const unsigned blocks = persistent_grid(
+                resident_blocks<&k_frames<SF, MODE, LPHY_FRAMES_OCC>>(current_device()), (A.frames + WPB - 1) / WPB, 0);
+            P.waves = blocks * WPB;
+            hipLaunchKernelGGL((k_frames<SF, MODE, LPHY_FRAMES_OCC>), dim3(blocks), dim3(kTile), 0, st, P);
             HIP_OK(hipGetLastError());
             return 0;
         });
@@ -159,19 +149,18 @@ int launch_wave_sf(const DemodArgs& A, hipStream_t st) {
             FrameArgs P{};
             P.A = A;
             constexpr int WPB = wave_wpb<SF, MODE>();
-            unsigned long long blocks = (unsigned long long)cu_count();
-            const unsigned long long need = (A.frames + WPB - 1) / WPB;
-            if (blocks > need) blocks = need;
-            P.waves = (unsigned)(blocks * WPB);
+            // (a workgroup per CU: one wave per SIMD)
+            const unsigned blocks = persistent_grid(device_cus(current_device()), (A.frames + WPB - 1) / WPB, 0);
+            P.waves = blocks * WPB;
             if constexpr (lphy::wave_kernel(SF, MODE & 3, WIN, true)) {
                 if (lphy::wave_spans(SF, A.total_syms)) {
-                    hipLaunchKernelGGL((k_wave<SF, MODE, true>), dim3((unsigned)blocks), dim3(64 * WPB), 0, st, P);
+                    hipLaunchKernelGGL((k_wave<SF, MODE, true>), dim3(blocks), dim3(64 * WPB), 0, st, P);
                     HIP_OK(hipGetLastError());
                     return 0;
                 }
             }
             if constexpr (lphy::wave_kernel(SF, MODE & 3, WIN, false)) {
-                hipLaunchKernelGGL((k_wave<SF, MODE, false>), dim3((unsigned)blocks), dim3(64 * WPB), 0, st, P);
+                hipLaunchKernelGGL((k_wave<SF, MODE, false>), dim3(blocks), dim3(64 * WPB), 0, st, P);
                 HIP_OK(hipGetLastError());
                 return 0;
             } else {
@@ -210,18 +199,14 @@ int launch_ragged_sf(const RaggedArgs& R, hipStream_t st, unsigned grid_cap) {
         return -ENOTSUP;
     } else {
         using G = Geo<SF>;
-        constexpr int FPW = G::T >= 2 ? G::T / 2 : 1;
+        constexpr int FPW = rg_fpw<SF>();
         const unsigned long long frames = R.A.frames;
         hipLaunchKernelGGL(k_rg_prologue<SF>, dim3((unsigned)((frames + FPW - 1) / FPW)), dim3(kTile), 0, st, R);
         with_mode<true, false>(R.A.mode, R.A.win != nullptr, false, [&](auto m) {
             constexpr int MODE = decltype(m)::value;
-            unsigned long long grid = (unsigned long long)resident_grid<&k_rg_demod<SF, MODE>>();
-            if (R.units_hint) {
-                const unsigned long long tiles = (R.units_hint + G::T - 1) / G::T;
-                if (grid > tiles) grid = tiles;
-            }
-            if (grid_cap && grid > grid_cap) grid = grid_cap;
-            hipLaunchKernelGGL((k_rg_demod<SF, MODE>), dim3((unsigned)grid), dim3(kTile), 0, st, R);
+            const unsigned grid = persistent_grid(resident_blocks<&k_rg_demod<SF, MODE>>(current_device()),
+                                                  (R.units_hint + G::T - 1) / G::T, grid_cap);
+            hipLaunchKernelGGL((k_rg_demod<SF, MODE>), dim3(grid), dim3(kTile), 0, st, R);
             return 0;
         });
         hipLaunchKernelGGL(k_rg_final<SF>, dim3((unsigned)((frames + kTile - 1) / kTile)), dim3(kTile), 0, st, R);
@@ -230,64 +215,26 @@ int launch_ragged_sf(const RaggedArgs& R, hipStream_t st, unsigned grid_cap) {
     }
 }
 
-// lphy_hip_detect_batch (lphy_detect.h), SF 7-12: one persistent launch over
-// tiles of Geo<SF>::T windows (grid_cap as in launch_ragged_sf).
-template <int SF>
-int launch_detect_sf(const DetectArgs& D, hipStream_t st, unsigned grid_cap) {
-    if constexpr (SF < 7) {
-        (void)D; (void)st; (void)grid_cap;
-        return -ENOTSUP;
-    } else {
-        auto go = [&](auto p) {
-            constexpr int PREP = decltype(p)::value;
-            constexpr int T = Geo<SF>::T;
-            unsigned long long grid = (unsigned long long)resident_grid<&k_detect<SF, PREP>>();
-            const unsigned long long tiles = (D.windows + T - 1) / T;
-            if (grid > tiles) grid = tiles;
-            if (grid_cap && grid > grid_cap) grid = grid_cap;
-            hipLaunchKernelGGL((k_detect<SF, PREP>), dim3((unsigned)grid), dim3(kTile), 0, st, D);
-        };
-        const int prep = (D.dechirp ? kPrepDechirp : 0) | (D.win ? kPrepWindow : 0);
-        switch (prep) {
-            case 0: go(std::integral_constant<int, 0>{}); break;
-            case kPrepDechirp: go(std::integral_constant<int, kPrepDechirp>{}); break;
-            case kPrepWindow: go(std::integral_constant<int, kPrepWindow>{}); break;
-            default: go(std::integral_constant<int, kPrepDechirp | kPrepWindow>{}); break;
-        }
-        HIP_OK(hipGetLastError());
-        return 0;
-    }
-}
+// lphy_hip_detect_batch and lphy_hip_detect_ragged (lphy_detect.h), SF 7-12:
+// one persistent launch over tiles of Geo<SF>::T units.  The grid covers the
+// call's units when the host knows them (the lattice's windows, the table's
+// units_hint), else as in launch_ragged_sf; grid_cap as there.
+inline unsigned long long det_units_hint(const DetLattice& g) { return g.windows; }
+inline unsigned long long det_units_hint(const DetRagged& g) { return g.units_hint; }
 
-// lphy_hip_detect_ragged (lphy_detect.h), SF 7-12: one persistent launch over
-// tiles of Geo<SF>::T whole symbols.  The grid covers the call's units when
-// the host knows them (units_hint), else the resident grid launches and the
-// workgroups past the last unit leave at once (grid_cap as in
-// launch_ragged_sf).
-template <int SF>
-int launch_detect_ragged_sf(const DetectRaggedArgs& R, hipStream_t st, unsigned grid_cap) {
+template <int SF, class GEO>
+int launch_detect_sf(const DetectArgs& D, const GEO& geo, hipStream_t st, unsigned grid_cap) {
     if constexpr (SF < 7) {
-        (void)R; (void)st; (void)grid_cap;
+        (void)D; (void)geo; (void)st; (void)grid_cap;
         return -ENOTSUP;
     } else {
-        auto go = [&](auto p) {
+        with_prep(D.dechirp != 0, D.win != nullptr, [&](auto p) {
             constexpr int PREP = decltype(p)::value;
             constexpr int T = Geo<SF>::T;
-            unsigned long long grid = (unsigned long long)resident_grid<&k_detect_ragged<SF, PREP>>();
-            if (R.units_hint) {
-                const unsigned long long tiles = (R.units_hint + T - 1) / T;
-                if (grid > tiles) grid = tiles;
-            }
-            if (grid_cap && grid > grid_cap) grid = grid_cap;
-            hipLaunchKernelGGL((k_detect_ragged<SF, PREP>), dim3((unsigned)grid), dim3(kTile), 0, st, R);
-        };
-        const int prep = (R.D.dechirp ? kPrepDechirp : 0) | (R.D.win ? kPrepWindow : 0);
-        switch (prep) {
-            case 0: go(std::integral_constant<int, 0>{}); break;
-            case kPrepDechirp: go(std::integral_constant<int, kPrepDechirp>{}); break;
-            case kPrepWindow: go(std::integral_constant<int, kPrepWindow>{}); break;
-            default: go(std::integral_constant<int, kPrepDechirp | kPrepWindow>{}); break;
-        }
+            const unsigned grid = persistent_grid(resident_blocks<&k_detect<SF, PREP, GEO>>(current_device()),
+                                                  (det_units_hint(geo) + T - 1) / T, grid_cap);
+            hipLaunchKernelGGL((k_detect<SF, PREP, GEO>), dim3(grid), dim3(kTile), 0, st, D, geo);
+        });
         HIP_OK(hipGetLastError());
         return 0;
     }
@@ -302,14 +249,14 @@ int launch_estimate_sf(const DemodArgs& A, hipStream_t st) {
 }
 
 // lphy_hip_estimate_ragged (lphy_ragged.h), SF 7-12: one launch, a workgroup
-// per group of FPW frames (k_rg_prologue's grouping).
+// per group of rg_fpw frames (k_rg_prologue's grouping).
 template <int SF>
 int launch_estimate_ragged_sf(const RaggedArgs& R, unsigned long long est_samples, hipStream_t st) {
     if constexpr (SF < 7) {
         (void)R; (void)est_samples; (void)st;
         return -ENOTSUP;
     } else {
-        constexpr int FPW = Geo<SF>::T >= 2 ? Geo<SF>::T / 2 : 1;
+        constexpr int FPW = rg_fpw<SF>();
         hipLaunchKernelGGL(k_rg_estimate<SF>, dim3((unsigned)((R.A.frames + FPW - 1) / FPW)), dim3(kTile), 0, st, R,
                            est_samples);
         HIP_OK(hipGetLastError());

@@ -15,8 +15,9 @@
 // out_per_frame of one frame, frame index 0), so the end clamp, the max-abs
 // extent and the output slots are the frame's own and the uniform kernels are
 // compiled from unchanged code.  From there: the prologue's max-abs reduction
-// (workgroup_max) and the unit-to-frame search (unit_frame, shared with the
-// ragged transmit, lphy_tx.h).  The prologue's estimate pass is estimate_unit
+// (workgroup_max) and the tables' trip into LDS (load_tables); the unit's
+// frame and record come from ragged_unit (lphy_ragged_unit.h, shared with the
+// ragged detector and transmit).  The prologue's estimate pass is estimate_unit
 // written out (at SF 12 the helper cost registers and a wave per SIMD): a
 // change to it is made here too.
 // Exactness: every product a non-finite value could reach is redone with the
@@ -27,6 +28,7 @@
 #pragma once
 #include "lphy_demod.h"
 #include "lphy_final.h"
+#include "lphy_ragged_unit.h"
 
 namespace {
 
@@ -66,8 +68,13 @@ __device__ __forceinline__ int length_status(int mode, unsigned long long sample
     return 0;
 }
 
+// Frames per workgroup of the prologue and of k_rg_estimate, and so of their
+// launchers' grids (lphy_launch.h): half a tile's symbols, two per frame.
+template <int SF>
+constexpr int rg_fpw() { return Geo<SF>::T >= 2 ? Geo<SF>::T / 2 : 1; }
+
 // ---------------------------------------------------------------------------
-// Prologue.  A workgroup takes FPW = T / 2 consecutive frames (one at SF
+// Prologue.  A workgroup takes FPW = rg_fpw consecutive frames (one at SF
 // 11-12): it scans them one after the other with all its threads (modes 1/2),
 // then transforms their 2 FPW estimate symbols in one tile pass (two at
 // SF 12, whose tile holds one symbol) and thread k folds frame k.
@@ -76,7 +83,7 @@ template <int SF>
 __global__ __launch_bounds__(kTile) void k_rg_prologue(RaggedArgs R) {
     using G = Geo<SF>;
     constexpr int N = G::N, T = G::T;
-    constexpr int FPW = T >= 2 ? T / 2 : 1;
+    constexpr int FPW = rg_fpw<SF>();
     constexpr int PASSES = (2 * FPW + T - 1) / T;
     __shared__ cf32 lds[T * G::SSTRIDE];
     __shared__ cf32 twl[N];
@@ -90,7 +97,7 @@ __global__ __launch_bounds__(kTile) void k_rg_prologue(RaggedArgs R) {
     const int mode = R.A.mode;
     const unsigned long long nframes = R.A.frames;
     const unsigned long long f0 = (unsigned long long)blockIdx.x * FPW;
-    for (int i = tid; i < N; i += kTile) twl[i] = R.A.tw[i];
+    load_tables<N, false, false>(R.A, twl);
 
     // (1) length checks and normalisation, frame by frame
     for (int k = 0; k < FPW; ++k) {
@@ -206,9 +213,10 @@ __global__ __launch_bounds__(kTile) void k_rg_prologue(RaggedArgs R) {
 
 // ---------------------------------------------------------------------------
 // Symbols.  Persistent grid over tiles of T units; a team (the LPS lanes of
-// one symbol) finds its unit's frame by binary search over unit_offset: the
-// last record whose offset is <= u.  From SF 10 a symbol fills at least one
-// wavefront, so the search runs on wave-uniform values; below, once per team.
+// one symbol) finds its unit's frame by binary search over unit_offset
+// (ragged_unit): the last record whose offset is <= u.  From SF 10 a symbol
+// fills at least one wavefront, so the search runs on wave-uniform values;
+// below, once per team.
 // Staging as k_demod's exact path (stage_symbol: per-sample sincos, the large-
 // argument form where the phase needs it); a NaN bin sends the wave's (SF <=
 // 10) or the workgroup's symbols through the Annex G products once more, in
@@ -233,13 +241,8 @@ __global__ __launch_bounds__(kTile, SF <= 10 ? 2 : 1) void k_rg_demod(RaggedArgs
     if ((unsigned long long)blockIdx.x * T >= units) return;  // uniform
 
     const int tid = threadIdx.x;
-    for (int i = tid; i < N; i += kTile) {
-        twl[i] = R.A.tw[i];
-        if constexpr (TAB) {
-            if ((MODE & 3) != LPHY_MODE_LORA_DEMODULATE) dnl[i] = R.A.down[i];
-            if constexpr ((MODE & kWinBit) != 0) wnl[i] = R.A.win[i];
-        }
-    }
+    // (mode 1 reads no down-chirp)
+    load_tables<N, TAB && (MODE & 3) != LPHY_MODE_LORA_DEMODULATE, TAB && (MODE & kWinBit) != 0>(R.A, twl, dnl, wnl);
     __syncthreads();
     const cf32* down = TAB ? dnl : R.A.down;
     const float* win = (MODE & kWinBit) ? (TAB ? wnl : R.A.win) : nullptr;
@@ -248,19 +251,12 @@ __global__ __launch_bounds__(kTile, SF <= 10 ? 2 : 1) void k_rg_demod(RaggedArgs
     const Stage<SF> stg(slot, lam);
     const unsigned long long stride = (unsigned long long)gridDim.x * T;
     for (unsigned long long t0 = (unsigned long long)blockIdx.x * T; t0 < units; t0 += stride) {
-        unsigned long long u = t0 + (unsigned)slot;
-        if constexpr (G::LPS >= 64) {  // one symbol per wavefront or more: scalar search
-            const unsigned lo32 = __builtin_amdgcn_readfirstlane((unsigned)u);
-            const unsigned hi32 = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-            u = ((unsigned long long)hi32 << 32) | lo32;
-        }
-        bool live = u < units;
-        const unsigned lo = live ? unit_frame(desc, nframes, u) : 0u;
-        const lphy_ragged_desc d = desc[lo];
-        const DemodArgs V = frame_view<SF>(R, lo, d);
-        const unsigned long long s64 = u - d.unit_offset;
-        // (a table whose prefix is wrong cannot lead outside the frame)
-        live = live && d.unit_offset <= u && s64 < V.total_syms && d.samples < 0x80000000ull;
+        // (one symbol per wavefront or more: scalar search)
+        const RaggedUnit ru = ragged_unit<G::LPS >= 64>(desc, nframes, units, t0 + (unsigned)slot);
+        const lphy_ragged_desc& d = ru.d;
+        const DemodArgs V = frame_view<SF>(R, ru.frame, d);
+        const unsigned long long s64 = ru.s;
+        const bool live = ru.live && s64 < V.total_syms && d.samples < 0x80000000ull;
         lphy_frame_meta m{};
         if (live) m = V.meta[0];
         SymCtx c = sym_ctx(V, 0u, live ? (unsigned)s64 : 0u, live, N, m);
@@ -352,7 +348,7 @@ template <int SF>
 __global__ __launch_bounds__(kTile) void k_rg_estimate(RaggedArgs R, unsigned long long est_samples) {
     using G = Geo<SF>;
     constexpr int N = G::N, T = G::T;
-    constexpr int FPW = T >= 2 ? T / 2 : 1;
+    constexpr int FPW = rg_fpw<SF>();
     __shared__ cf32 lds[T * G::SSTRIDE];
     __shared__ cf32 twl[N];
     __shared__ ArgMax red[kTile / 64];
@@ -366,7 +362,7 @@ __global__ __launch_bounds__(kTile) void k_rg_estimate(RaggedArgs R, unsigned lo
     const unsigned step = (unsigned)N * (unsigned)osr;
     const unsigned long long nframes = R.A.frames;
     const unsigned long long f0 = (unsigned long long)blockIdx.x * FPW;
-    for (int i = tid; i < N; i += kTile) twl[i] = R.A.tw[i];
+    load_tables<N, false, false>(R.A, twl);
 
     // (1) the frame of thread k < FPW: status, estimate symbols, units
     int st = 0;

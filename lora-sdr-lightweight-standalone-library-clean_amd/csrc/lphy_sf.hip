@@ -18,9 +18,9 @@ template int launch_wave_sf<LPHY_SF>(const DemodArgs&, hipStream_t);
 template int launch_post_sf<LPHY_SF>(int, const DemodArgs&, const FinalArgs&, bool, bool, hipStream_t);
 template int launch_estimate_sf<LPHY_SF>(const DemodArgs&, hipStream_t);
 template int launch_ragged_sf<LPHY_SF>(const RaggedArgs&, hipStream_t, unsigned);
-template int launch_detect_sf<LPHY_SF>(const DetectArgs&, hipStream_t, unsigned);
+template int launch_detect_sf<LPHY_SF, DetLattice>(const DetectArgs&, const DetLattice&, hipStream_t, unsigned);
+template int launch_detect_sf<LPHY_SF, DetRagged>(const DetectArgs&, const DetRagged&, hipStream_t, unsigned);
 template int launch_estimate_ragged_sf<LPHY_SF>(const RaggedArgs&, unsigned long long, hipStream_t);
-template int launch_detect_ragged_sf<LPHY_SF>(const DetectRaggedArgs&, hipStream_t, unsigned);
 }  // namespace
 
 #ifdef LPHY_DEBUG_BOUNDS
@@ -53,9 +53,9 @@ const SfOps LPHY_CAT(sf_ops_, LPHY_SF) = {
     nullptr,
 #endif
     &launch_ragged_sf<LPHY_SF>,
-    &launch_detect_sf<LPHY_SF>,
+    &launch_detect_sf<LPHY_SF, DetLattice>,
     &launch_estimate_ragged_sf<LPHY_SF>,
-    &launch_detect_ragged_sf<LPHY_SF>,
+    &launch_detect_sf<LPHY_SF, DetRagged>,
 };
 }  // namespace lphy
 #endif

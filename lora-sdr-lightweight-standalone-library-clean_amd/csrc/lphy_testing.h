@@ -9,9 +9,10 @@
 // them from the environment; the product library's dispatch depends on the
 // call's arguments and lphy_hip_ctx_set_fused_min_frames alone.
 //   * lphy_hip_test_grid_cap(ctx, blocks), per context (0 restores the
-//     default): the persistent grids of k_rg_demod, k_detect, k_detect_ragged and k_tx_samples
-//     get min(grid, blocks) workgroups, after the launchers' own caps
-//     (units_hint, the call's tiles).  Those kernels are launched with
+//     default): the persistent grids of k_rg_demod, k_detect (both
+//     geometries) and k_tx_samples get min(grid, blocks) workgroups, after the
+//     launchers' own caps (units_hint, the call's tiles): the last argument
+//     of persistent_grid (lphy_args.h).  Those kernels are launched with
 //     min(resident grid, tiles of the call) workgroups, so their grid-stride
 //     loops take a second trip only in a call with more tiles than the device
 //     holds workgroups; under a cap of 1 one workgroup walks every tile, under

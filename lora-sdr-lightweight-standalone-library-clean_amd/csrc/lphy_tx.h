@@ -18,7 +18,8 @@
 //                 the phase at each symbol's start in the real part of that
 //                 symbol's own first output sample;
 //   k_tx_samples  persistent grid over tiles of kTile units (symbols); a lane
-//                 finds its unit's frame by binary search over unit_offset,
+//                 finds its unit's frame by binary search over unit_offset
+//                 (ragged_unit, lphy_ragged_unit.h),
 //                 reads its parked phase, and the wave then regenerates its 64
 //                 symbols chunk by chunk: every lane walks kTxChunk phases of
 //                 its own symbol into its LDS row, then the lanes regroup
@@ -31,6 +32,7 @@
 // the unit stores to the unit's row, after the barrier that follows the read.
 #pragma once
 #include "lphy_mod.h"
+#include "lphy_ragged_unit.h"
 
 namespace {
 
@@ -160,13 +162,11 @@ __global__ __launch_bounds__(kTile) void k_tx_samples(TxArgs A, SRC src) {
     const int rr = lane / kTxRowLanes, rj = lane % kTxRowLanes;  // store phase: row within the group, pair within the row
     const unsigned long long stride = (unsigned long long)gridDim.x * kTile;
     for (unsigned long long t0 = (unsigned long long)blockIdx.x * kTile; t0 < units; t0 += stride) {
-        const unsigned long long u = t0 + (unsigned)tid;
-        bool live = u < units;
-        const lphy_ragged_desc d = desc[live ? unit_frame(desc, nframes, u) : 0u];
-        const unsigned long long s = u - d.unit_offset;
-        // (a table whose prefix is wrong cannot lead outside the frame; the
-        // byte form's odd last symbol is not modulated)
-        live = live && d.unit_offset <= u && s < tx_symbols<SRC>(d, step);
+        const RaggedUnit ru = ragged_unit<false>(desc, nframes, units, t0 + (unsigned)tid);
+        const lphy_ragged_desc& d = ru.d;
+        const unsigned long long s = ru.s;
+        // (the byte form's odd last symbol is not modulated)
+        const bool live = ru.live && s < tx_symbols<SRC>(d, step);
         cf32* row = live ? A.iq + d.iq_offset + s * step : nullptr;
         float phase = 0.0f, fr = 0.0f;
         if (live) {

@@ -1,5 +1,5 @@
-"""lphy_hip_detect_ragged / lphy_hip_detect_ragged_host (k_detect_ragged,
-csrc/lphy_detect.h): the reference's LoRaDetector::detect on every whole
+"""lphy_hip_detect_ragged / lphy_hip_detect_ragged_host (k_detect over the
+DetRagged geometry, csrc/lphy_detect.h): the reference's LoRaDetector::detect on every whole
 symbol of every frame of a lphy_ragged_desc table in one launch, the record
 of symbol s of frame f at unit_offset[f] + s.
 
