@@ -44,6 +44,7 @@
 // follows per window is one function, detect_window.
 #pragma once
 #include "lphy_demod.h"
+#include "lphy_ragged_layout.h"
 #include "lphy_ragged_unit.h"
 
 namespace {
@@ -202,7 +203,7 @@ __device__ __forceinline__ DetUnit det_unit(const DetRagged& g, unsigned long lo
     const RaggedUnit ru = ragged_unit<Geo<SF>::LPS >= 64>(g.desc, g.frames, units, u);
     // whole symbols of the frame (samples < 2^31 where it counts)
     const unsigned n = ((unsigned)ru.d.samples >> SF) / g.osr;
-    const bool live = ru.live && ru.d.samples < 0x80000000ull && ru.s < n;
+    const bool live = ru.live && ru.d.samples < kRaggedMaxSamples && ru.s < n;
     const unsigned long long fstep = (unsigned long long)Geo<SF>::N * g.osr;
     return DetUnit{ru.d.iq_offset + (live ? ru.s : 0) * fstep + g.phase, g.osr, ru.d.iq_offset + n * fstep,
                    ru.d.unit_offset + ru.s, live};

@@ -15,6 +15,7 @@
 #include "lphy_lorawan_ragged.h"
 #include "lphy_testing.h"
 
+#include <climits>
 #include <cmath>
 #include <complex>
 #include <cstring>
@@ -434,13 +435,13 @@ int lphy_hip_ctx_set_fused_min_frames(lphy_hip_ctx* c, long frames) {
 }
 
 size_t lphy_hip_syms_per_frame(const lphy_hip_ctx* c, size_t frame_samples, int mode) {
-    if (!c) return 0;
-    const size_t total = frame_samples / ((size_t)c->N * c->osr);
-    if (mode == LPHY_MODE_DEMODULATE) return total >= 2 ? total - 2 : 0;
-    return total >= 2 ? total - 2 : total;
+    return c ? ragged_out_syms(frame_samples / ((size_t)c->N * c->osr), mode) : 0;
 }
 
 namespace {
+// what the ragged entry points' argument checks read of a context (lphy_ragged_layout.h)
+RaggedCtx ragged_ctx(const lphy_hip_ctx* c) { return c ? RaggedCtx{true, c->sf, c->osr} : RaggedCtx{}; }
+
 int demod_batch_impl(lphy_hip_ctx* c, const float* d_iq, size_t frames, size_t frame_samples,
                      uint16_t* d_syms, uint8_t* d_bytes, lphy_frame_meta* d_meta, int mode,
                      unsigned flags, hipStream_t st, void* lent_spec);
@@ -490,8 +491,7 @@ int demod_batch_impl(lphy_hip_ctx* c, const float* d_iq, size_t frames, size_t f
     A.exact_rotation = (flags & LPHY_F_EXACT_ROTATION) ? 1 : 0;
     A.spec = (mode != LPHY_MODE_DEMODULATE && !A.no_scratch && !(flags & LPHY_F_SCAN_FIRST)) ? 1 : 0;
     A.debug_recheck = (flags & LPHY_F_DEBUG_RECHECK) ? 1 : 0;
-    const size_t est_syms = mode == LPHY_MODE_DEMODULATE ? 2 : (total < 2 ? total : 2);
-    A.est_units = (int)(est_syms * c->osr);
+    A.est_units = (int)(ragged_est_syms(total, mode) * c->osr);
     // 32-bit symbol / sample bookkeeping in the kernels
     if (frames > 0x7fffffffULL || frames * (total ? total : 1) >= 0xffffffffULL ||
         frame_samples >= 0x7fffffffULL)
@@ -558,13 +558,6 @@ namespace {
 int demod_ragged_impl(lphy_hip_ctx* c, const float* d_iq, const lphy_ragged_desc* d_desc, size_t frames,
                       uint16_t* d_syms, uint8_t* d_bytes, lphy_frame_meta* d_meta, int mode, unsigned flags,
                       hipStream_t st, unsigned long long units_hint) {
-    if (!c || !d_iq || !d_desc || !d_meta || !d_syms) return -EINVAL;
-    if (mode < 0 || mode > 2) return -EINVAL;
-    if (flags & ~(unsigned)(LPHY_F_DECODE | LPHY_F_NO_SCRATCH)) return -ENOTSUP;
-    if (c->osr != 1 || c->sf < 7) return -ENOTSUP;
-    if ((flags & LPHY_F_DECODE) && !d_bytes) return -EINVAL;
-    if (frames == 0) return 0;
-    if (frames > 0x7fffffffULL) return -ERANGE;
     const SfOps* ops = sf_ops(c->sf);
     if (!ops || !ops->ragged) return -ENOTSUP;  // (an experiment build without this SF's object)
     HIP_OK(hipSetDevice(c->device));
@@ -591,6 +584,8 @@ int demod_ragged_impl(lphy_hip_ctx* c, const float* d_iq, const lphy_ragged_desc
 int lphy_hip_demod_ragged(lphy_hip_ctx* c, const float* d_iq, const lphy_ragged_desc* d_desc, size_t frames,
                           uint16_t* d_syms, uint8_t* d_bytes, lphy_frame_meta* d_meta, int mode,
                           unsigned flags, void* stream) {
+    if (int rc = demod_ragged_args(ragged_ctx(c), d_iq && d_desc && d_meta && d_syms, mode, flags, d_bytes, frames))
+        return rc > 0 ? 0 : rc;
     return demod_ragged_impl(c, d_iq, d_desc, frames, d_syms, d_bytes, d_meta, mode, flags, (hipStream_t)stream, 0);
 }
 
@@ -640,20 +635,6 @@ int lphy_hip_detect_batch(lphy_hip_ctx* c, const float* d_iq, size_t total_sampl
 
 // ---- the detector on a ragged table (k_detect over DetRagged, lphy_detect.h)
 namespace {
-// The argument checks of both forms, in the header's order (before any device
-// call): 0 to go on, 1 when there is nothing to do, or the error.
-int detect_ragged_check(const lphy_hip_ctx* c, const void* iq, const void* desc, size_t frames, unsigned phase,
-                        const void* out, unsigned flags) {
-    if (!c) return -EINVAL;
-    if (frames == 0) return 1;
-    if (!iq || !desc || !out) return -EINVAL;
-    if (flags & ~(unsigned)LPHY_DET_DECHIRP) return -EINVAL;
-    if (phase >= c->osr) return -EINVAL;
-    if (frames > 0x7fffffffULL) return -ERANGE;
-    if (c->sf < 7) return -ENOTSUP;
-    return 0;
-}
-
 // units_hint: the call's whole symbols when the caller's table is on the host
 int detect_ragged_impl(lphy_hip_ctx* c, const float* d_iq, const lphy_ragged_desc* d_desc, size_t frames,
                        unsigned phase, lphy_detect_rec* d_out, unsigned flags, hipStream_t st,
@@ -673,7 +654,8 @@ int detect_ragged_impl(lphy_hip_ctx* c, const float* d_iq, const lphy_ragged_des
 
 int lphy_hip_detect_ragged(lphy_hip_ctx* c, const float* d_iq, const lphy_ragged_desc* d_desc, size_t frames,
                            unsigned phase, lphy_detect_rec* d_out, unsigned flags, void* stream) {
-    if (int rc = detect_ragged_check(c, d_iq, d_desc, frames, phase, d_out, flags)) return rc > 0 ? 0 : rc;
+    if (int rc = detect_ragged_args(ragged_ctx(c), frames, d_iq && d_desc && d_out, phase, flags))
+        return rc > 0 ? 0 : rc;
     return detect_ragged_impl(c, d_iq, d_desc, frames, phase, d_out, flags, (hipStream_t)stream, 0);
 }
 
@@ -721,7 +703,7 @@ int lphy_hip_estimate_batch(lphy_hip_ctx* c, const float* d_iq, size_t frames,
     // the estimate may not leave its frame (the last frame's would leave the buffer)
     if (est_samples > frame_samples) return -EINVAL;
     if (syms == 0) return 0;  // phy.cpp:87,91: nothing written
-    if (syms * c->osr > 0x7fffffffULL) return -ERANGE;
+    if (syms * c->osr > (size_t)INT_MAX) return -ERANGE;  // A.est_units
     HIP_OK(hipSetDevice(c->device));
     DemodArgs A{};
     ctx_args(c, A);
@@ -738,18 +720,6 @@ int lphy_hip_estimate_batch(lphy_hip_ctx* c, const float* d_iq, size_t frames,
 }
 
 namespace {
-// The argument checks of both forms of the ragged estimate, in the header's
-// order (before any device call): 0 to go on, 1 when there is nothing to do,
-// or the error.
-int estimate_ragged_check(const lphy_hip_ctx* c, const void* iq, const void* desc, size_t frames, const void* meta) {
-    if (!c) return -EINVAL;
-    if (frames == 0) return 1;
-    if (!iq || !desc || !meta) return -EINVAL;
-    if (frames > 0x7fffffffULL) return -ERANGE;
-    if (c->sf < 7) return -ENOTSUP;
-    return 0;
-}
-
 int estimate_ragged_impl(lphy_hip_ctx* c, const float* d_iq, const lphy_ragged_desc* d_desc, size_t frames,
                          size_t est_samples, lphy_frame_meta* d_meta, hipStream_t st) {
     const SfOps* ops = sf_ops(c->sf);
@@ -770,7 +740,7 @@ int estimate_ragged_impl(lphy_hip_ctx* c, const float* d_iq, const lphy_ragged_d
 
 int lphy_hip_estimate_ragged(lphy_hip_ctx* c, const float* d_iq, const lphy_ragged_desc* d_desc, size_t frames,
                              size_t est_samples, lphy_frame_meta* d_meta, void* stream) {
-    if (int rc = estimate_ragged_check(c, d_iq, d_desc, frames, d_meta)) return rc > 0 ? 0 : rc;
+    if (int rc = ragged_args(ragged_ctx(c), frames, d_iq && d_desc && d_meta)) return rc > 0 ? 0 : rc;
     return estimate_ragged_impl(c, d_iq, d_desc, frames, est_samples, d_meta, (hipStream_t)stream);
 }
 
@@ -835,7 +805,7 @@ int compensate_batch_check(const lphy_hip_ctx* c, const float* in, const float* 
     if (!c) return -EINVAL;
     if (frames == 0) return 1;
     if (!in || !out || !meta) return -EINVAL;
-    if (frames > 0x7fffffffULL) return -ERANGE;
+    if (frames > kRaggedMaxFrames) return -ERANGE;
     if (frame_samples == 0) return 1;
     size_t bytes = 0;
     if (__builtin_mul_overflow(frames, frame_samples, &bytes) || __builtin_mul_overflow(bytes, sizeof(cf32), &bytes))
@@ -992,10 +962,7 @@ int lphy_hip_compensate_batch(lphy_hip_ctx* c, const float* d_in, float* d_out, 
 
 int lphy_hip_compensate_ragged(lphy_hip_ctx* c, const float* d_in, float* d_out, const lphy_ragged_desc* d_desc,
                                size_t frames, const lphy_frame_meta* d_meta, void* stream) {
-    if (!c) return -EINVAL;
-    if (frames == 0) return 0;
-    if (!d_in || !d_out || !d_desc || !d_meta) return -EINVAL;
-    if (frames > 0x7fffffffULL) return -ERANGE;
+    if (int rc = ragged_args(ragged_ctx(c), frames, d_in && d_out && d_desc && d_meta, 0)) return rc > 0 ? 0 : rc;
     HIP_OK(hipSetDevice(c->device));
     return compensate_batch_launch(c, d_in, d_out, CompRagged{d_desc}, frames, kCompRaggedSlots, d_meta,
                                    (hipStream_t)stream);
@@ -1030,17 +997,6 @@ int lphy_hip_lorawan_tx_layout(const lphy_hip_ctx* c, const lphy_lorawan_tx* h_t
 size_t lphy_hip_symbol_samples(const lphy_hip_ctx* c) { return c ? (size_t)c->N * c->osr : 0; }
 
 namespace {
-// The argument checks the three forms share, in the header's order (`src`: the
-// symbols or the bytes): 0 to go on, 1 when there is nothing to do, or the error.
-int tx_check(const lphy_hip_ctx* c, const void* src, const void* desc, size_t frames, const void* iq) {
-    if (!c) return -EINVAL;
-    if (frames == 0) return 1;
-    if (!src || !desc || !iq) return -EINVAL;
-    if (frames > 0x7fffffffULL) return -ERANGE;
-    if (c->sf < 7) return -ENOTSUP;
-    return 0;
-}
-
 extern "C++" {
 // The two launches.  units_hint: the call's whole symbols when the caller's
 // table is on the host (the sample pass's grid then stops at its tiles).
@@ -1071,14 +1027,14 @@ int tx_launch(const lphy_hip_ctx* c, SRC src, const lphy_ragged_desc* d_desc, si
 
 int lphy_hip_modulate_ragged(lphy_hip_ctx* c, const uint16_t* d_syms, const lphy_ragged_desc* d_desc, size_t frames,
                              float* d_iq, float amplitude, uint8_t sync, void* stream) {
-    if (int rc = tx_check(c, d_syms, d_desc, frames, d_iq)) return rc > 0 ? 0 : rc;
+    if (int rc = ragged_args(ragged_ctx(c), frames, d_syms && d_desc && d_iq)) return rc > 0 ? 0 : rc;
     HIP_OK(hipSetDevice(c->device));
     return tx_launch(c, TxSymbols{d_syms}, d_desc, frames, d_iq, nullptr, amplitude, sync, (hipStream_t)stream, 0);
 }
 
 int lphy_hip_tx_ragged(lphy_hip_ctx* c, const uint8_t* d_bytes, const lphy_ragged_desc* d_desc, size_t frames,
                        float* d_iq, uint16_t* d_syms_out, float amplitude, uint8_t sync, void* stream) {
-    if (int rc = tx_check(c, d_bytes, d_desc, frames, d_iq)) return rc > 0 ? 0 : rc;
+    if (int rc = ragged_args(ragged_ctx(c), frames, d_bytes && d_desc && d_iq)) return rc > 0 ? 0 : rc;
     HIP_OK(hipSetDevice(c->device));
     return tx_launch(c, TxBytes{d_bytes}, d_desc, frames, d_iq, d_syms_out, amplitude, sync, (hipStream_t)stream, 0);
 }

@@ -144,14 +144,9 @@ int lphy_hip_demod_host(lphy_hip_ctx* c, const float* h_iq, size_t frames,
 int lphy_hip_demod_ragged_host(lphy_hip_ctx* c, const float* h_iq, const lphy_ragged_desc* h_desc, size_t frames,
                                uint16_t* h_syms, uint8_t* h_bytes, lphy_frame_meta* h_meta, int mode,
                                unsigned flags) {
-    if (!c || !h_desc || !h_meta) return -EINVAL;
-    if (mode < 0 || mode > 2) return -EINVAL;
-    if (flags & ~(unsigned)(LPHY_F_DECODE | LPHY_F_NO_SCRATCH)) return -ENOTSUP;
-    if (c->osr != 1 || c->sf < 7) return -ENOTSUP;
+    if (int rc = demod_ragged_args(ragged_ctx(c), h_desc && h_meta, mode, flags, h_bytes, frames))
+        return rc > 0 ? 0 : rc;
     const bool decode = (flags & LPHY_F_DECODE) != 0;
-    if (decode && !h_bytes) return -EINVAL;
-    if (frames == 0) return 0;
-    if (frames > 0x7fffffffULL) return -ERANGE;
     uint64_t iq_samples = 0, out_syms = 0;
     if (int rc = ragged_extent(c->N, h_desc, frames, mode, &iq_samples, &out_syms)) return rc;
     if ((iq_samples && !h_iq) || (out_syms && !h_syms)) return -EINVAL;
@@ -183,7 +178,8 @@ int lphy_hip_detect_host(lphy_hip_ctx* c, const float* h_iq, size_t total_sample
 // the table's whole symbols, that many records out.
 int lphy_hip_detect_ragged_host(lphy_hip_ctx* c, const float* h_iq, const lphy_ragged_desc* h_desc, size_t frames,
                                 unsigned phase, lphy_detect_rec* h_out, unsigned flags) {
-    if (int rc = detect_ragged_check(c, h_iq, h_desc, frames, phase, h_out, flags)) return rc > 0 ? 0 : rc;
+    if (int rc = detect_ragged_args(ragged_ctx(c), frames, h_iq && h_desc && h_out, phase, flags))
+        return rc > 0 ? 0 : rc;
     uint64_t iq_samples = 0, units = 0;
     if (int rc = detect_ragged_extent((uint64_t)c->N * c->osr, h_desc, frames, &iq_samples, &units)) return rc;
     if (units == 0) return 0;  // no frame holds a whole symbol: nothing is written
@@ -217,7 +213,7 @@ int lphy_hip_estimate_host(lphy_hip_ctx* c, const float* h_iq, size_t count,
 // record of a frame without a whole symbol comes back as it went).
 int lphy_hip_estimate_ragged_host(lphy_hip_ctx* c, const float* h_iq, const lphy_ragged_desc* h_desc, size_t frames,
                                   size_t est_samples, lphy_frame_meta* h_meta) {
-    if (int rc = estimate_ragged_check(c, h_iq, h_desc, frames, h_meta)) return rc > 0 ? 0 : rc;
+    if (int rc = ragged_args(ragged_ctx(c), frames, h_iq && h_desc && h_meta)) return rc > 0 ? 0 : rc;
     uint64_t iq_samples = 0;
     if (int rc = estimate_ragged_extent(h_desc, frames, &iq_samples)) return rc;
     HostCall hc(c, kPageable);
@@ -261,11 +257,8 @@ int lphy_hip_modulate_host(lphy_hip_ctx* c, const uint16_t* h_syms, size_t nsyms
 // launches, IQ and symbols out.  The table is checked before any device call.
 int lphy_hip_tx_ragged_host(lphy_hip_ctx* c, const uint8_t* h_bytes, const lphy_ragged_desc* h_desc, size_t frames,
                             float* h_iq, uint16_t* h_syms_out, float amplitude, uint8_t sync) {
-    if (!c) return -EINVAL;
-    if (frames == 0) return 0;
-    if (!h_desc || !h_iq) return -EINVAL;
-    if (frames > 0x7fffffffULL) return -ERANGE;
-    if (c->sf < 7) return -ENOTSUP;
+    // (whether the bytes are needed is the table's to say)
+    if (int rc = ragged_args(ragged_ctx(c), frames, h_desc && h_iq)) return rc > 0 ? 0 : rc;
     TxExtent x;
     if (int rc = tx_extent((uint64_t)c->N * c->osr, h_desc, frames, &x)) return rc;
     if (x.in_bytes && !h_bytes) return -EINVAL;

@@ -654,7 +654,7 @@ int lphy_hip_lorawan_build_ragged(const uint8_t* d_src, const lphy_lorawan_tx* d
     if (!frames) return 0;
     if (!d_src || !d_tx || !d_desc || !d_keys || !d_bytes || !d_status || !symbol_samples || !nkeys) return -EINVAL;
     if (reinterpret_cast<uintptr_t>(d_keys) & 15 || reinterpret_cast<uintptr_t>(d_tx) & 15) return -EINVAL;
-    if (frames > 0x7fffffffULL) return -ERANGE;
+    if (frames > kRaggedMaxFrames) return -ERANGE;
     hipLaunchKernelGGL(k_lw_build, dim3(grid_for(frames)), dim3(kThreads), kLds, (hipStream_t)stream, d_src, d_tx,
                        d_desc, (unsigned long long)frames, (unsigned long long)symbol_samples, d_keys,
                        (unsigned long long)nkeys, d_bytes, d_syms_out, d_status);
@@ -672,7 +672,7 @@ int lphy_hip_lorawan_parse_ragged(const uint8_t* d_bytes, const lphy_ragged_desc
     if (mode < 0 || mode > 2) return -EINVAL;
     if (reinterpret_cast<uintptr_t>(d_keys) & 15 || reinterpret_cast<uintptr_t>(d_out) & 15) return -EINVAL;
     if ((d_key_index && d_sessions) || (d_sessions && !nsessions)) return -EINVAL;
-    if (frames > 0x7fffffffULL) return -ERANGE;
+    if (frames > kRaggedMaxFrames) return -ERANGE;
     hipLaunchKernelGGL(k_lw_parse_ragged, dim3(grid_for(frames)), dim3(kThreads), kLds, (hipStream_t)stream, d_bytes,
                        d_desc, (unsigned long long)frames, (unsigned long long)symbol_samples, mode, d_meta, d_keys,
                        (unsigned long long)nkeys, d_key_index, d_sessions,
@@ -690,7 +690,7 @@ int lphy_hip_lorawan_crypt_batch(uint8_t* d_bytes, const lphy_lorawan_desc* d_de
     if (!jobs) return 0;
     if (!d_bytes || !d_desc || !d_keys || !nkeys) return -EINVAL;
     if (reinterpret_cast<uintptr_t>(d_keys) & 15 || reinterpret_cast<uintptr_t>(d_desc) & 15) return -EINVAL;
-    if (jobs > 0x7fffffffULL) return -ERANGE;
+    if (jobs > kRaggedMaxFrames) return -ERANGE;
     return launch_crypt(d_bytes, CryptBatch{d_desc}, jobs, d_keys, nkeys, d_status, stream);
 }
 
@@ -700,7 +700,7 @@ int lphy_hip_lorawan_crypt_tx_ragged(uint8_t* d_src, const lphy_lorawan_tx* d_tx
     if (!frames) return 0;
     if (!d_src || !d_tx || !d_keys || !nkeys || skip > 1) return -EINVAL;
     if (reinterpret_cast<uintptr_t>(d_keys) & 15 || reinterpret_cast<uintptr_t>(d_tx) & 15) return -EINVAL;
-    if (frames > 0x7fffffffULL) return -ERANGE;
+    if (frames > kRaggedMaxFrames) return -ERANGE;
     return launch_crypt(d_src, CryptTx{d_tx, skip}, frames, d_keys, nkeys, d_status, stream);
 }
 
@@ -712,7 +712,7 @@ int lphy_hip_lorawan_crypt_rx_ragged(uint8_t* d_bytes, const lphy_ragged_desc* d
     if (!d_bytes || !d_desc || !d_parsed || !d_keys || !nkeys || !symbol_samples || skip > 1) return -EINVAL;
     if (mode < 0 || mode > 2) return -EINVAL;
     if (reinterpret_cast<uintptr_t>(d_keys) & 15 || reinterpret_cast<uintptr_t>(d_parsed) & 15) return -EINVAL;
-    if (frames > 0x7fffffffULL) return -ERANGE;
+    if (frames > kRaggedMaxFrames) return -ERANGE;
     return launch_crypt(d_bytes, CryptRx{d_desc, d_parsed, d_key_used, (unsigned long long)symbol_samples, mode, skip},
                         frames, d_keys, nkeys, d_status, stream);
 }

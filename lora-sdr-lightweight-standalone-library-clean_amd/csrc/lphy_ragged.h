@@ -28,6 +28,7 @@
 #pragma once
 #include "lphy_demod.h"
 #include "lphy_final.h"
+#include "lphy_ragged_layout.h"
 #include "lphy_ragged_unit.h"
 
 namespace {
@@ -42,7 +43,6 @@ __device__ __forceinline__ DemodArgs frame_view(const RaggedArgs& R, unsigned lo
                                                 const lphy_ragged_desc& d) {
     DemodArgs V = R.A;
     const unsigned long long total = d.samples >> SF;
-    const bool raw = R.A.mode == LPHY_MODE_DEMODULATE;
     bound_check((long long)f, (long long)R.A.frames);
     V.iq = R.A.iq + d.iq_offset;
     V.syms = R.A.syms + d.sym_offset;
@@ -50,15 +50,15 @@ __device__ __forceinline__ DemodArgs frame_view(const RaggedArgs& R, unsigned lo
     V.frames = 1;
     V.frame_samples = d.samples;
     V.total_syms = total;
-    V.out_per_frame = total >= 2 ? total - 2 : (raw ? 0 : total);
-    V.est_units = raw ? 2 : (int)(total < 2 ? total : 2);
+    V.out_per_frame = ragged_out_syms(total, R.A.mode);
+    V.est_units = (int)ragged_est_syms(total, R.A.mode);
     return V;
 }
 
 // The frame's status from its length alone: the conditions the uniform call
 // returns before it launches anything (lphy_hip_demod_batch)
 __device__ __forceinline__ int length_status(int mode, unsigned long long samples, int N) {
-    if (samples >= 0x80000000ull) return -ERANGE;  // 32-bit sample bookkeeping (sym_ctx)
+    if (samples >= kRaggedMaxSamples) return -ERANGE;  // 32-bit sample bookkeeping (sym_ctx)
     const unsigned long long total = samples / (unsigned)N;
     if (mode == LPHY_MODE_DEMODULATE) {
         if (samples % (unsigned)N) return -EINVAL;  // phy.cpp:190-194
@@ -145,7 +145,7 @@ __global__ __launch_bounds__(kTile) void k_rg_prologue(RaggedArgs R) {
                 m.status = st;
             }
             fm[k] = m;
-            fest[k] = mode == LPHY_MODE_DEMODULATE ? 2 : (int)(total < 2 ? total : 2);
+            fest[k] = (int)ragged_est_syms(total, mode);
         }
         __syncthreads();
     }
@@ -256,7 +256,7 @@ __global__ __launch_bounds__(kTile, SF <= 10 ? 2 : 1) void k_rg_demod(RaggedArgs
         const lphy_ragged_desc& d = ru.d;
         const DemodArgs V = frame_view<SF>(R, ru.frame, d);
         const unsigned long long s64 = ru.s;
-        const bool live = ru.live && s64 < V.total_syms && d.samples < 0x80000000ull;
+        const bool live = ru.live && s64 < V.total_syms && d.samples < kRaggedMaxSamples;
         lphy_frame_meta m{};
         if (live) m = V.meta[0];
         SymCtx c = sym_ctx(V, 0u, live ? (unsigned)s64 : 0u, live, N, m);
@@ -321,7 +321,7 @@ __global__ __launch_bounds__(kTile) void k_rg_final(RaggedArgs R) {
     F.bytes = R.bytes ? R.bytes + d.sym_offset / 2 : nullptr;
     F.meta = R.A.meta + f;
     F.frames = 1;
-    F.nsyms = total >= 2 ? total - 2 : (R.A.mode == LPHY_MODE_DEMODULATE ? 0 : total);
+    F.nsyms = ragged_out_syms(total, R.A.mode);
     F.sym_stride = F.nsyms;
     F.shift = R.shift;
     F.decode = R.decode;
@@ -373,7 +373,7 @@ __global__ __launch_bounds__(kTile) void k_rg_estimate(RaggedArgs R, unsigned lo
         unsigned long long off = 0;
         if (mine) {
             const lphy_ragged_desc d = R.desc[f0 + tid];
-            if (d.samples >= 0x80000000ull) {
+            if (d.samples >= kRaggedMaxSamples) {
                 st = -ERANGE;  // the ragged demodulator's rule (length_status)
             } else {
                 const unsigned long long e = est_samples && est_samples < d.samples ? est_samples : d.samples;

@@ -339,14 +339,23 @@ class Demodulator:
                                              desc.ctypes.data), "lphy_hip_ragged_layout")
         return desc
 
-    def _ragged_extent(self, desc: np.ndarray, mode: int):
-        """(IQ samples, output symbols) the descriptors span."""
+    def _ragged_extents(self, desc: np.ndarray, mode: int):
+        """(IQ samples, output symbols, whole symbols, bytes a transmit call
+        reads) the descriptors span."""
         d = desc[:-1]
         total = d["samples"] // np.uint64(self.N * self.osr)
-        per = np.where(total >= 2, total - np.minimum(total, 2), 0 if mode == MODE_DEMODULATE else total)
-        iq = int((d["iq_offset"] + d["samples"]).max()) if d.size else 0
-        out = int((d["sym_offset"] + per.astype(np.uint64)).max()) if d.size else 0
-        return iq, out
+        data = total - np.minimum(total, 2)  # behind the two sync symbols
+        per = np.where(total >= 2, data, 0 if mode == MODE_DEMODULATE else total).astype(np.uint64)
+
+        def top(a):
+            return int(a.max()) if a.size else 0
+        return (top(d["iq_offset"] + d["samples"]), top(d["sym_offset"] + per), int(desc["unit_offset"][-1]),
+                top(d["sym_offset"] // np.uint64(2) + data // np.uint64(2)))
+
+    def _ragged_extent(self, desc: np.ndarray, mode: int):
+        """(IQ samples, output symbols) the descriptors span: for callers that
+        size device buffers themselves."""
+        return self._ragged_extents(desc, mode)[:2]
 
     def demod_ragged(self, iq, desc, frames, syms, meta, mode, flags=0, payload=None, stream=None,
                      iq_samples=None, out_syms=None):
@@ -376,7 +385,7 @@ class Demodulator:
         desc = np.ascontiguousarray(a) if a.dtype == RAGGED_DESC_DTYPE else self.ragged_layout(a, mode)
         frames = desc.size - 1
         iq = np.ascontiguousarray(iq_flat, np.complex64).reshape(-1)
-        n_iq, n_out = self._ragged_extent(desc, mode)
+        n_iq, n_out, _, _ = self._ragged_extents(desc, mode)
         if iq.size < n_iq:
             raise ValueError(f"iq: {iq.size} samples, the descriptors span {n_iq}")
         syms = np.full(max(n_out, 1), fill, np.uint16)
@@ -438,11 +447,9 @@ class Demodulator:
                 else self.ragged_layout(a, MODE_DEMODULATE))
         frames = desc.size - 1
         iq = np.ascontiguousarray(iq_flat, np.complex64).reshape(-1)
-        d = desc[:-1]
-        n_iq = int((d["iq_offset"] + d["samples"]).max()) if d.size else 0
+        n_iq, _, units, _ = self._ragged_extents(desc, MODE_DEMODULATE)
         if iq.size < n_iq:
             raise ValueError(f"iq: {iq.size} samples, the descriptors span {n_iq}")
-        units = int(desc["unit_offset"][-1])
         out = np.zeros(units, DETECT_DTYPE)
         pad = np.zeros(1, np.complex64)
         opad = np.zeros(1, DETECT_DTYPE)
@@ -523,10 +530,7 @@ class Demodulator:
             desc = np.ascontiguousarray(desc, RAGGED_DESC_DTYPE)
             data = np.ascontiguousarray(payloads_or_data, np.uint8).reshape(-1)
         frames = desc.size - 1
-        n_iq, n_out = self._ragged_extent(desc, MODE_LORA_DEMODULATE)
-        d = desc[:-1]
-        total = np.maximum(d["samples"] // np.uint64(self.N * self.osr), np.uint64(2))
-        need = int((d["sym_offset"] // np.uint64(2) + (total - np.uint64(2)) // np.uint64(2)).max()) if frames else 0
+        n_iq, n_out, _, need = self._ragged_extents(desc, MODE_LORA_DEMODULATE)
         if data.size < need:
             raise ValueError(f"data: {data.size} bytes, the descriptors read {need}")
         if iq is None:
@@ -678,8 +682,7 @@ class Demodulator:
                 else self.ragged_layout(a, MODE_DEMODULATE))
         frames = desc.size - 1
         iq = np.ascontiguousarray(iq_flat, np.complex64).reshape(-1)
-        d = desc[:-1]
-        n_iq = int((d["iq_offset"] + d["samples"]).max()) if d.size else 0
+        n_iq = self._ragged_extents(desc, MODE_DEMODULATE)[0]
         if iq.size < n_iq:
             raise ValueError(f"iq: {iq.size} samples, the descriptors span {n_iq}")
         m = (np.zeros(frames, META_DTYPE) if meta is None

@@ -2,23 +2,13 @@
 // csrc/lphy_ragged_layout.h for lphy_hip_detect_ragged_host: its staging
 // plan, the reservation and the table check it makes before any device call
 // (tests/test_detect_ragged_plan_cpu.py loads it through ctypes).
-#include "lphy_stage_plan.h"
+#include "plan_dump.h"
 
 using namespace lphy;
 
-// out: n, end, copied_end, up.begin, up.end, down.begin, down.end, then
-// (off, size, role) per slice.  Returns the number of values written.
+// out: plan_dump's
 extern "C" int detect_ragged_plan_check(uint64_t iq_samples, uint64_t frames, uint64_t units, uint64_t* out) {
-    const StagePlan p = detect_ragged_plan(iq_samples, frames, units);
-    const uint64_t head[7] = {(uint64_t)p.n, p.end, p.copied_end, p.up.begin, p.up.end, p.down.begin, p.down.end};
-    int k = 0;
-    for (uint64_t v : head) out[k++] = v;
-    for (int i = 0; i < p.n; ++i) {
-        out[k++] = p.s[i].off;
-        out[k++] = p.s[i].size;
-        out[k++] = p.s[i].role;
-    }
-    return k;
+    return plan_dump(detect_ragged_plan(iq_samples, frames, units), out);
 }
 
 extern "C" uint64_t detect_ragged_reserve_check(uint64_t N, uint64_t osr, uint64_t frames, uint64_t frame_samples,

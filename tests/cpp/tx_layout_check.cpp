@@ -3,7 +3,7 @@
 // context of (sf, osr); tx_extent: the table checks of
 // lphy_hip_tx_ragged_host) and csrc/lphy_stage_plan.h (tx_plan), without a
 // device (tests/test_tx_layout_cpu.py loads it through ctypes).
-#include "lphy_stage_plan.h"
+#include "plan_dump.h"
 
 using namespace lphy;
 
@@ -31,20 +31,9 @@ extern "C" int tx_extent_check(unsigned sf, unsigned osr, const lphy_ragged_desc
     return 0;
 }
 
-// a: in_bytes, frames, iq_samples, out_syms, iq_gaps, sym_gaps.  out: n, end,
-// copied_end, up.begin, up.end, down.begin, down.end, then (off, size, role)
-// per slice.  Returns the number of values written.
+// a: in_bytes, frames, iq_samples, out_syms, iq_gaps, sym_gaps.  out: plan_dump's.
 extern "C" int tx_plan_check(const uint64_t* a, uint64_t* out) {
-    const StagePlan p = tx_plan(a[0], a[1], a[2], a[3], a[4] != 0, a[5] != 0);
-    const uint64_t head[7] = {(uint64_t)p.n, p.end, p.copied_end, p.up.begin, p.up.end, p.down.begin, p.down.end};
-    int k = 0;
-    for (uint64_t v : head) out[k++] = v;
-    for (int i = 0; i < p.n; ++i) {
-        out[k++] = p.s[i].off;
-        out[k++] = p.s[i].size;
-        out[k++] = p.s[i].role;
-    }
-    return k;
+    return plan_dump(tx_plan(a[0], a[1], a[2], a[3], a[4] != 0, a[5] != 0), out);
 }
 
 extern "C" uint64_t tx_reserve_check(uint64_t N, uint64_t osr, uint64_t frames, uint64_t frame_samples,

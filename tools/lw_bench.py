@@ -5,7 +5,8 @@ usage: python tools/lw_bench.py [frames] [row_bytes]
        python tools/lw_bench.py ragged [frames] [out.json]
 The ragged case (default 65,536 frames of mixed lengths 12..64 bytes on one
 lphy_ragged_desc table) times lphy_hip_lorawan_parse_ragged and
-lphy_hip_lorawan_build_ragged against the routes without them:
+lphy_hip_lorawan_build_ragged against the routes without them (and, on its
+own, lphy_hip_lorawan_crypt_rx_ragged over the rows the parse accepted):
   parse  a device gather of the packed bytes into padded rows (index and mask
          tensors made beforehand, a length array) + lphy_hip_lorawan_parse_batch;
   build  the frames' MHDR..FRMPayload assembled on the host (not timed), then
@@ -148,13 +149,27 @@ def ragged(nf, out_path, rounds=7):
     torch.cuda.synchronize()
     assert torch.equal(t_out, t_ref), "the two parse routes disagree"
 
+    # the payload cipher on the rows the parse accepted, in place (applied twice it restores them)
+    t_plain = t_rows.clone()
+
+    def crypt_rx():
+        lphy.lorawan_crypt_rx_ragged(t_plain, t_desc, t_out, nf, N, 1, keys, stream=st, out_syms=2 * total)
+
+    crypt_rx()
+    torch.cuda.synchronize()
+    assert not torch.equal(t_plain, t_rows)
+    crypt_rx()
+    torch.cuda.synchronize()
+    assert torch.equal(t_plain, t_rows), "the cipher applied twice does not restore the rows"
+
     res = {k: [] for k in ("parse_ragged", "parse_gather_batch", "build_ragged_kernel", "mic_batch_kernel",
-                           "build_ragged_with_upload", "mic_batch_with_upload")}
+                           "crypt_rx_ragged", "build_ragged_with_upload", "mic_batch_with_upload")}
     for _ in range(rounds):
         res["parse_ragged"].append(timed(parse_new, 200))
         res["parse_gather_batch"].append(timed(parse_old, 200))
         res["build_ragged_kernel"].append(timed(build_new_kernel, 200))
         res["mic_batch_kernel"].append(timed(build_old_kernel, 200))
+        res["crypt_rx_ragged"].append(timed(crypt_rx, 200))
         res["build_ragged_with_upload"].append(walled(build_new, 50))
         res["mic_batch_with_upload"].append(walled(build_old, 50))
     out = {"frames": nf, "frame_bytes": "12..64", "total_bytes": total, "rounds": rounds,
