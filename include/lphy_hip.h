@@ -28,6 +28,8 @@
  *                          over a batch of windows (lphy_detect_rec, below)
  *   lphy_hip_detect_ragged the same on every whole symbol of every frame of
  *                          a ragged table (lphy_ragged_desc, below)
+ *   lphy_hip_find_frames   no reference function: the ragged table of the
+ *                          frames found in a capture, from those records
  *   lphy_hip_decode_batch  lora_phy::decode / lora_decode on device symbols
  *   lphy_hip_estimate_batch lora_phy::estimate_offsets src/phy/phy.cpp:81-148
  *   lphy_hip_estimate_ragged the same for frames of different lengths in one
@@ -356,6 +358,93 @@ int lphy_hip_detect_ragged_host(lphy_hip_ctx* ctx, const float* h_iq,
                                 const lphy_ragged_desc* h_desc, size_t frames,
                                 unsigned phase, lphy_detect_rec* h_out,
                                 unsigned flags);
+
+/* ------------------------------------------------------------------------
+ * Frame search: the ragged table of the frames found in a capture, from the
+ * detector records of its windows.  No reference function: the reference's
+ * waveform has no preamble (two sync symbols, then data, LoRaMod.cpp:8-43) and
+ * it has no search.  The result is a pure function of the records, which
+ * lphy_hip_detect_batch pins to the reference's detector bit for bit, so the
+ * receive chain starts at the capture with no host read between the calls:
+ *   lphy_hip_detect_batch (hop <= N) -> lphy_hip_find_frames ->
+ *   lphy_hip_estimate_ragged -> lphy_hip_compensate_ragged ->
+ *   lphy_hip_demod_ragged -> lphy_hip_lorawan_parse_ragged -> ..._crypt_rx_ragged
+ *
+ * With S = lphy_hip_symbol_samples(ctx) and p = *params:
+ *   1. Window w is active iff (rec[w].power - rec[w].power_avg) >=
+ *      p.threshold_db, the subtraction and the compare in float32.  A NaN
+ *      difference is inactive: the all-zero window (both fields -inf) is.
+ *   2. Two consecutive active windows a < a' belong to one burst iff a' - a - 1
+ *      <= p.max_gap.  A burst is (a, b), its first and last active window;
+ *      inactive windows before the first and after the last active one are
+ *      never bridged.
+ *   3. start = p.first + p.lead + a * p.hop.  extent = 0 when start >=
+ *      p.total_samples, else min((b - a + 1) * p.hop, p.total_samples - start).
+ *      total = extent / S.  The frame is total * S samples at start: whole
+ *      symbols, never overlapping another frame, never leaving the capture.
+ *   4. Drops, in this order: total < p.min_symbols counts in dropped_short;
+ *      total * S >= 2^31 counts in dropped_long.
+ *   5. The kept bursts, in order of a, are frames 0, 1, ...  Those past
+ *      max_frames count in overflow and are not written.
+ *   6. Record k of a frame is {iq_offset = start, samples = total * S,
+ *      sym_offset, unit_offset}: sym_offset the exclusive prefix of
+ *      (lphy_hip_syms_per_frame(total * S, mode) + 1) & ~1, unit_offset the
+ *      exclusive prefix of total, exactly as lphy_hip_ragged_layout packs them.
+ *   7. Records frames .. max_frames, the last included, hold the totals of the
+ *      frames written: {end of the last frame (0 with none), 0, the symbol
+ *      total, the unit total}.  The table is therefore valid for every ragged
+ *      call with frames = max_frames: the padding frames have 0 samples, which
+ *      all of those calls define, record [max_frames] is the totals record, and
+ *      no host read of d_info is needed to go on.
+ *   8. The call writes all max_frames + 1 records and d_info, and nothing else
+ *      outside d_work.  The result does not depend on what d_work held and is
+ *      the same on every run (no atomic decides an order).
+ *
+ * d_work: lphy_hip_find_frames_workspace(windows) bytes of device memory,
+ * 16-byte aligned (never 0 bytes).  The device form is asynchronous on
+ * `stream`: six launches whatever the arguments, no device allocation, no host
+ * read of anything on the device, and no workgroup waits on another (the
+ * order between the passes is the order of the launches).  Every SF is in
+ * scope: there is no transform.  The host form goes through the context's
+ * stream and staging like lphy_hip_detect_host and takes its workspace from
+ * that staging.
+ *
+ * Returns, all before any device call and in this order: -EINVAL for a null
+ * ctx, params, d_desc or d_info; d_rec null with windows > 0; d_work null or
+ * not 16-byte aligned; hop == 0, min_symbols == 0 or max_frames == 0; a NaN
+ * threshold; reserved != 0; a mode outside 0..2.  -ERANGE for windows >= 2^32;
+ * max_frames > 2^31 - 1; first + lead + windows * hop > 2^48; windows * hop / S
+ * >= 2^32 (each computed without overflow).  windows == 0 is not an early
+ * return: it writes the all-padding table and a zero d_info.
+ * --------------------------------------------------------------------- */
+typedef struct lphy_find_params {      /* host memory, read on the host */
+    uint64_t first;          /* first sample of window 0 (lphy_hip_detect_batch's first)  */
+    uint64_t hop;            /* samples between window starts (its hop), >= 1             */
+    uint64_t lead;           /* samples added to every frame's start (the caller's        */
+                             /* calibration for overlapping windows; 0 when hop = symbol) */
+    uint64_t total_samples;  /* the capture's length: no frame reaches past it            */
+    float    threshold_db;   /* window active iff power - power_avg >= threshold_db       */
+    uint32_t max_gap;        /* up to this many inactive windows inside a burst are bridged */
+    uint32_t min_symbols;    /* bursts of fewer whole symbols are dropped, >= 1           */
+    uint32_t reserved;       /* 0 */
+} lphy_find_params;
+
+typedef struct lphy_find_info {        /* 32 bytes, device memory, written by the call */
+    uint32_t frames;         /* records 0 .. frames-1 of the table are real frames */
+    uint32_t bursts;         /* bursts found before any was dropped                */
+    uint32_t dropped_short, dropped_long, overflow;
+    uint32_t active;         /* active windows */
+    uint32_t reserved[2];    /* 0 */
+} lphy_find_info;
+
+size_t lphy_hip_find_frames_workspace(size_t windows);   /* bytes, host-only */
+int lphy_hip_find_frames(lphy_hip_ctx* ctx, const lphy_detect_rec* d_rec, size_t windows,
+                         const lphy_find_params* params, int mode, size_t max_frames,
+                         lphy_ragged_desc* d_desc /* max_frames + 1 records */,
+                         lphy_find_info* d_info, void* d_work, void* stream);
+int lphy_hip_find_frames_host(lphy_hip_ctx* ctx, const lphy_detect_rec* h_rec, size_t windows,
+                              const lphy_find_params* params, int mode, size_t max_frames,
+                              lphy_ragged_desc* h_desc, lphy_find_info* h_info);
 
 /* Hamming(8,4)sx decode + sx1272 CRC of device symbols: frame f holds
  * syms_per_frame symbols at d_syms + f*syms_per_frame and yields

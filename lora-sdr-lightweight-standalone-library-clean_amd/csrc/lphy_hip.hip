@@ -4,7 +4,7 @@
 // the kernels templated on SF are the lphy_sf.hip objects'), and the
 // SF-independent kernels themselves: the finalisation (k_finalize), the
 // modulator and the compensation (lphy_mod.h), the ragged transmit path
-// (lphy_tx.h), k_mark_recheck.  The host-
+// (lphy_tx.h), the frame search (lphy_find.h), k_mark_recheck.  The host-
 // buffer forms (*_host) are lphy_host.h, included at the end.
 #include "lphy_args.h"
 #include "lphy_final.h"
@@ -13,6 +13,7 @@
 #include "lphy_route.h"
 #include "lphy_stage_plan.h"
 #include "lphy_lorawan_ragged.h"
+#include "lphy_find.h"
 #include "lphy_testing.h"
 
 #include <climits>
@@ -659,6 +660,64 @@ int lphy_hip_detect_ragged(lphy_hip_ctx* c, const float* d_iq, const lphy_ragged
     return detect_ragged_impl(c, d_iq, d_desc, frames, phase, d_out, flags, (hipStream_t)stream, 0);
 }
 
+// ---- the frame search (lphy_find.h) ------------------------------------------
+size_t lphy_hip_find_frames_workspace(size_t windows) { return find_layout(windows).bytes; }
+
+namespace {
+int find_frames_check(const lphy_hip_ctx* c, const void* rec, size_t windows, const lphy_find_params* p, int mode,
+                      size_t max_frames, const void* desc, const void* info, bool work) {
+    return find_frames_args(ragged_ctx(c), p, desc && info, rec != nullptr, work, c ? (uint64_t)c->N * c->osr : 1,
+                            windows, mode, max_frames);
+}
+
+// The six launches; the arguments have passed find_frames_check.
+int find_frames_impl(lphy_hip_ctx* c, const lphy_detect_rec* d_rec, size_t windows, const lphy_find_params& p, int mode,
+                     size_t max_frames, lphy_ragged_desc* d_desc, lphy_find_info* d_info, void* d_work,
+                     hipStream_t st) {
+    HIP_OK(hipSetDevice(c->device));
+    const FindLayout l = find_layout(windows);
+    char* w = static_cast<char*>(d_work);
+    FindArgs A{};
+    A.rec = reinterpret_cast<const uint4*>(d_rec);
+    A.windows = windows;
+    A.geo = FindGeo{p.first, p.hop, p.lead, p.total_samples, (uint64_t)c->N * c->osr, p.max_gap, p.min_symbols, mode};
+    A.threshold = p.threshold_db;
+    A.max_frames = (unsigned)max_frames;
+    A.desc = d_desc;
+    A.info = d_info;
+    A.tiles = l.tiles;
+    A.totals = reinterpret_cast<FindTotals*>(w + l.totals);
+    A.bits = reinterpret_cast<unsigned long long*>(w + l.bits);
+    A.sums = reinterpret_cast<FindSum*>(w + l.sums);
+    A.carry = reinterpret_cast<uint2*>(w + l.carry);
+    A.counts = reinterpret_cast<FindTileCount*>(w + l.counts);
+    A.prefix = reinterpret_cast<FindTilePrefix*>(w + l.prefix);
+    const unsigned cap = test_grid_cap(c);
+    const unsigned g_flags = persistent_grid(resident_blocks<&k_find_flags>(c->device), l.tiles, cap);
+    const unsigned g_count = persistent_grid(resident_blocks<&k_find_count>(c->device), l.tiles, cap);
+    const unsigned g_write = persistent_grid(resident_blocks<&k_find_write>(c->device), l.tiles, cap);
+    const unsigned g_pad =
+        persistent_grid(resident_blocks<&k_find_pad>(c->device), ((unsigned long long)max_frames + kTile) / kTile, cap);
+    hipLaunchKernelGGL(k_find_flags, dim3(g_flags), dim3(kTile), 0, st, A);
+    hipLaunchKernelGGL(k_find_carry, dim3(1), dim3(kTile), 0, st, A);
+    hipLaunchKernelGGL(k_find_count, dim3(g_count), dim3(kTile), 0, st, A);
+    hipLaunchKernelGGL(k_find_offsets, dim3(1), dim3(kTile), 0, st, A);
+    hipLaunchKernelGGL(k_find_write, dim3(g_write), dim3(kTile), 0, st, A);
+    hipLaunchKernelGGL(k_find_pad, dim3(g_pad), dim3(kTile), 0, st, A);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+}  // namespace
+
+int lphy_hip_find_frames(lphy_hip_ctx* c, const lphy_detect_rec* d_rec, size_t windows, const lphy_find_params* p,
+                         int mode, size_t max_frames, lphy_ragged_desc* d_desc, lphy_find_info* d_info, void* d_work,
+                         void* stream) {
+    if (int rc = find_frames_check(c, d_rec, windows, p, mode, max_frames, d_desc, d_info,
+                                   d_work && ((uintptr_t)d_work & 15) == 0))
+        return rc;
+    return find_frames_impl(c, d_rec, windows, *p, mode, max_frames, d_desc, d_info, d_work, (hipStream_t)stream);
+}
+
 int lphy_hip_detect_serial_count(lphy_hip_ctx* c, unsigned long long* out, int reset) {
     return read_counters(c, kCtrDetectSerial, 1, out, reset);
 }
@@ -1070,7 +1129,7 @@ int lphy_hip_test_pinned_max(lphy_hip_ctx* c, size_t bytes) {
 }
 
 // Test build only: at most `blocks` workgroups in the persistent grids of
-// k_rg_demod, k_detect (both geometries) and k_tx_samples on this context, after the launchers'
+// k_rg_demod, k_detect (both geometries), k_tx_samples and the frame search on this context, after the launchers'
 // own caps (0: the default).  A small call then walks its grid-stride loops
 // more than once, which otherwise needs more tiles than the device holds
 // workgroups.

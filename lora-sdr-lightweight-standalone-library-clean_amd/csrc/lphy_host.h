@@ -189,6 +189,19 @@ int lphy_hip_detect_ragged_host(lphy_hip_ctx* c, const float* h_iq, const lphy_r
                                         hc.dev<lphy_detect_rec>(2), flags, hc.stream(), units));
 }
 
+// The frame search on host buffers: the records in, the six launches with the
+// workspace lent from the staging, the table and the info out.
+int lphy_hip_find_frames_host(lphy_hip_ctx* c, const lphy_detect_rec* h_rec, size_t windows, const lphy_find_params* p,
+                              int mode, size_t max_frames, lphy_ragged_desc* h_desc, lphy_find_info* h_info) {
+    if (int rc = find_frames_check(c, h_rec, windows, p, mode, max_frames, h_desc, h_info, true)) return rc;
+    HostCall hc(c, kPageable);
+    if (int rc = hc.begin(find_plan(windows, max_frames, find_layout(windows).bytes), {h_rec, h_desc, h_info}))
+        return rc;
+    return hc.finish(find_frames_impl(c, hc.dev<lphy_detect_rec>(0), windows, *p, mode, max_frames,
+                                      hc.dev<lphy_ragged_desc>(1), hc.dev<lphy_find_info>(2), hc.dev<void>(3),
+                                      hc.stream()));
+}
+
 int lphy_hip_decode_host(lphy_hip_ctx* c, const uint16_t* h_syms, size_t count,
                          uint8_t* h_bytes, lphy_frame_meta* h_meta) {
     if (!c || !h_syms || !h_bytes || !h_meta) return -EINVAL;

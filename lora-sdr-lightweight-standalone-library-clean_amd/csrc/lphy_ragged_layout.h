@@ -5,7 +5,7 @@
 // forms check it with, and the entry points' argument checks.  Plain C++ with
 // LPHY_RG_HD in front of what the kernels call too, no HIP: the CPU tests
 // compile it alone (tests/cpp/ragged_layout_check.cpp, ragged_walk_check.cpp,
-// tx_layout_check.cpp).
+// tx_layout_check.cpp, find_frames_check.cpp).
 #pragma once
 #include <cerrno>
 #include <cstddef>
@@ -205,6 +205,31 @@ constexpr int demod_ragged_args(RaggedCtx c, bool ptrs, int mode, unsigned flags
     if ((flags & LPHY_F_DECODE) && !bytes) return -EINVAL;
     if (frames == 0) return 1;
     if (frames > kRaggedMaxFrames) return -ERANGE;
+    return 0;
+}
+
+// find_frames.  ptrs: the table and the info are there; rec: the records are
+// (asked for with windows > 0 only); work: the workspace is there and 16-byte
+// aligned (the host form lends its own: true); step = N * osr, of a context
+// that is not null.  windows == 0 goes on: the call writes the padding.  The
+// two sums are bounded by division, so neither wraps.
+inline int find_frames_args(RaggedCtx c, const lphy_find_params* p, bool ptrs, bool rec, bool work, uint64_t step,
+                            uint64_t windows, int mode, uint64_t max_frames) {
+    if (!c.ok || !p || !ptrs) return -EINVAL;
+    if (windows > 0 && !rec) return -EINVAL;
+    if (!work) return -EINVAL;
+    if (p->hop == 0 || p->min_symbols == 0 || max_frames == 0) return -EINVAL;
+    if (p->threshold_db != p->threshold_db) return -EINVAL;
+    if (p->reserved != 0) return -EINVAL;
+    if (mode < 0 || mode > 2) return -EINVAL;
+    if (windows >= kRaggedMaxUnits) return -ERANGE;
+    if (max_frames > kRaggedMaxFrames) return -ERANGE;
+    // first + lead + windows * hop <= 2^48
+    if (p->first > kRaggedMaxOffset || p->lead > kRaggedMaxOffset - p->first) return -ERANGE;
+    const uint64_t room = kRaggedMaxOffset - p->first - p->lead;
+    if (windows && p->hop > room / windows) return -ERANGE;
+    // windows * hop / step < 2^32 (the product is at most 2^48 here)
+    if (windows * p->hop / step >= kRaggedMaxUnits) return -ERANGE;
     return 0;
 }
 

@@ -150,6 +150,19 @@ inline StagePlan detect_ragged_plan(size_t iq_samples, size_t frames, size_t uni
         .add(units * sizeof(lphy_detect_rec), kStageOut);
 }
 
+// records | desc (max_frames + 1 records) | info | the search's workspace
+// (find_layout's bytes, lphy_find_scan.h) - lphy_hip_find_frames_host.  Not
+// among the plans lphy_hip_ctx_reserve sizes for: a capture's windows and the
+// table's capacity are not a frame shape, so a call past the reservation grows
+// the staging once, like any other.
+inline StagePlan find_plan(size_t windows, size_t max_frames, size_t work_bytes) {
+    return StagePlan()
+        .add(windows * sizeof(lphy_detect_rec), kStageIn)
+        .add((max_frames + 1) * sizeof(lphy_ragged_desc), kStageOut)
+        .add(sizeof(lphy_find_info), kStageOut)
+        .add(work_bytes, kStageScratch);
+}
+
 // Staging every *_host entry point needs for calls of up to `frames` frames
 // of `frame_samples` samples, or one buffer of frames * frame_samples: the
 // largest of the eleven plans at that shape (the ragged estimate's slices are

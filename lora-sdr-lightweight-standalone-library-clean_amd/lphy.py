@@ -94,6 +94,23 @@ DETECT_DTYPE = np.dtype([("power", "<f4"), ("power_avg", "<f4"), ("findex", "<f4
 assert DETECT_DTYPE.itemsize == 16
 DET_DECHIRP = 1  # lphy_hip_detect_*: the context's down-chirp on every window first
 
+# lphy_find_params / lphy_find_info (include/lphy_hip.h): the frame search
+FIND_PARAMS = np.dtype([("first", "<u8"), ("hop", "<u8"), ("lead", "<u8"), ("total_samples", "<u8"),
+                        ("threshold_db", "<f4"), ("max_gap", "<u4"), ("min_symbols", "<u4"), ("reserved", "<u4")])
+assert FIND_PARAMS.itemsize == 48
+FIND_INFO = np.dtype([("frames", "<u4"), ("bursts", "<u4"), ("dropped_short", "<u4"), ("dropped_long", "<u4"),
+                      ("overflow", "<u4"), ("active", "<u4"), ("reserved", "<u4", (2,))])
+assert FIND_INFO.itemsize == 32
+FIND_TILE = 1024  # windows per tile of the search's passes (csrc/lphy_find_scan.h kFindTile)
+
+
+def find_params(first=0, hop=0, lead=0, total_samples=0, threshold_db=0.0, max_gap=0, min_symbols=1,
+                reserved=0) -> np.ndarray:
+    """One FIND_PARAMS record."""
+    p = np.zeros(1, FIND_PARAMS)
+    p[0] = (first, hop, lead, total_samples, threshold_db, max_gap, min_symbols, reserved)
+    return p
+
 _vp = C.c_void_p
 _sz = C.c_size_t
 
@@ -115,6 +132,7 @@ EXPORTS = (
     "lphy_hip_modulate_ragged", "lphy_hip_tx_ragged", "lphy_hip_tx_ragged_host", "lphy_hip_tx_layout",
     "lphy_hip_estimate_ragged", "lphy_hip_estimate_ragged_host",
     "lphy_hip_detect_ragged", "lphy_hip_detect_ragged_host",
+    "lphy_hip_find_frames_workspace", "lphy_hip_find_frames", "lphy_hip_find_frames_host",
     "lphy_hip_symbol_samples", "lphy_hip_lorawan_build_ragged", "lphy_hip_lorawan_tx_layout",
     "lphy_hip_lorawan_parse_ragged", "lphy_hip_lorawan_sessions_check",
     "lphy_hip_lorawan_crypt_batch", "lphy_hip_lorawan_crypt_tx_ragged", "lphy_hip_lorawan_crypt_rx_ragged",
@@ -180,6 +198,10 @@ def load(path: Path | None = None) -> C.CDLL:
     L.lphy_hip_detect_serial_count.argtypes = [_vp, C.POINTER(C.c_ulonglong), C.c_int]
     L.lphy_hip_detect_ragged.argtypes = [_vp, _vp, _vp, _sz, C.c_uint, _vp, C.c_uint, _vp]
     L.lphy_hip_detect_ragged_host.argtypes = [_vp, _vp, _vp, _sz, C.c_uint, _vp, C.c_uint]
+    L.lphy_hip_find_frames_workspace.argtypes = [_sz]
+    L.lphy_hip_find_frames_workspace.restype = _sz
+    L.lphy_hip_find_frames.argtypes = [_vp, _vp, _sz, _vp, C.c_int, _sz, _vp, _vp, _vp, _vp]
+    L.lphy_hip_find_frames_host.argtypes = [_vp, _vp, _sz, _vp, C.c_int, _sz, _vp, _vp]
     L.lphy_hip_decode_batch.argtypes = [_vp, _vp, _sz, _sz, _vp, _vp, _vp]
     L.lphy_hip_estimate_batch.argtypes = [_vp, _vp, _sz, _sz, _sz, _vp, _vp]
     L.lphy_hip_estimate_ragged.argtypes = [_vp, _vp, _vp, _sz, _sz, _vp, _vp]
@@ -458,6 +480,45 @@ class Demodulator:
                                                   (out if units else opad).ctypes.data, flags),
              "lphy_hip_detect_ragged_host")
         return out, desc
+
+    # --- the frame search (lphy_hip_find_frames*) ------------------------
+    def find_frames_workspace(self, windows: int) -> int:
+        """Bytes of device workspace find_frames needs for `windows` records."""
+        return int(self.lib.lphy_hip_find_frames_workspace(windows))
+
+    def find_frames(self, rec, windows, params, mode, max_frames, desc, info, work, stream=None):
+        """The ragged table of the frames found in a capture, from the detector
+        records of its windows (lphy_hip_find_frames).  `rec`: device tensor of
+        `windows` DETECT_DTYPE records (detect_batch's output; may be None for
+        windows == 0); `params`: one FIND_PARAMS record (find_params());
+        `desc`: device tensor of max_frames + 1 RAGGED_DESC_DTYPE records, all
+        written, valid for every ragged call with frames = max_frames; `info`:
+        device tensor of one FIND_INFO record; `work`: device tensor of
+        find_frames_workspace(windows) bytes.  Asynchronous."""
+        dv = self.device
+        prm = np.ascontiguousarray(params, FIND_PARAMS).reshape(-1)
+        if prm.size != 1:
+            raise ValueError(f"params: one FIND_PARAMS record expected, got {prm.size}")
+        p_rec = _dev_buf(rec, "rec", dv, windows * 16, None) if (windows or rec is not None) else None
+        p_desc = _dev_buf(desc, "desc", dv, (max_frames + 1) * 32, None)
+        p_info = _dev_buf(info, "info", dv, 32, None)
+        p_work = _dev_buf(work, "work", dv, self.find_frames_workspace(windows), None)
+        _chk(self.lib.lphy_hip_find_frames(self.ctx, p_rec, windows, prm.ctypes.data, mode, max_frames, p_desc,
+                                           p_info, p_work, stream), "lphy_hip_find_frames")
+
+    def find_frames_host(self, rec: np.ndarray, params, mode: int, max_frames: int):
+        """The same on host records; returns (desc, info): max_frames + 1
+        RAGGED_DESC_DTYPE records and the FIND_INFO record."""
+        r = np.ascontiguousarray(rec, DETECT_DTYPE).reshape(-1)
+        prm = np.ascontiguousarray(params, FIND_PARAMS).reshape(-1)
+        if prm.size != 1:
+            raise ValueError(f"params: one FIND_PARAMS record expected, got {prm.size}")
+        desc = np.zeros(max(max_frames, 0) + 1, RAGGED_DESC_DTYPE)
+        info = np.zeros(1, FIND_INFO)
+        _chk(self.lib.lphy_hip_find_frames_host(self.ctx, r.ctypes.data if r.size else None, r.size,
+                                                prm.ctypes.data, mode, max_frames, desc.ctypes.data,
+                                                info.ctypes.data), "lphy_hip_find_frames_host")
+        return desc, info[0]
 
     def detect_serial_count(self, reset: bool = True) -> int:
         """Windows whose power_avg took the in-order walk of the bins because
@@ -769,8 +830,8 @@ class Demodulator:
 
     def grid_cap(self, blocks: int) -> None:
         """Test build only: at most `blocks` workgroups in the persistent grids
-        of the ragged symbol kernel, the detector and the ragged transmit's
-        sample pass on this context (0: the default), so that a small call
+        of the ragged symbol kernel, the detector, the ragged transmit's
+        sample pass and the frame search on this context (0: the default), so that a small call
         walks their grid-stride loops more than once."""
         fn = self.lib.lphy_hip_test_grid_cap
         fn.argtypes = [_vp, C.c_uint]
