@@ -30,6 +30,8 @@
  *                          a ragged table (lphy_ragged_desc, below)
  *   lphy_hip_find_frames   no reference function: the ragged table of the
  *                          frames found in a capture, from those records
+ *   lphy_hip_channelize    no reference function: a wideband capture to the
+ *                          per-channel streams the calls above take
  *   lphy_hip_decode_batch  lora_phy::decode / lora_decode on device symbols
  *   lphy_hip_estimate_batch lora_phy::estimate_offsets src/phy/phy.cpp:81-148
  *   lphy_hip_estimate_ragged the same for frames of different lengths in one
@@ -366,7 +368,7 @@ int lphy_hip_detect_ragged_host(lphy_hip_ctx* ctx, const float* h_iq,
  * it has no search.  The result is a pure function of the records, which
  * lphy_hip_detect_batch pins to the reference's detector bit for bit, so the
  * receive chain starts at the capture with no host read between the calls:
- *   lphy_hip_detect_batch (hop <= N) -> lphy_hip_find_frames ->
+ *   lphy_hip_channelize -> lphy_hip_detect_batch (hop <= N) -> lphy_hip_find_frames ->
  *   lphy_hip_estimate_ragged -> lphy_hip_compensate_ragged ->
  *   lphy_hip_demod_ragged -> lphy_hip_lorawan_parse_ragged -> ..._crypt_rx_ragged
  *
@@ -445,6 +447,76 @@ int lphy_hip_find_frames(lphy_hip_ctx* ctx, const lphy_detect_rec* d_rec, size_t
 int lphy_hip_find_frames_host(lphy_hip_ctx* ctx, const lphy_detect_rec* h_rec, size_t windows,
                               const lphy_find_params* params, int mode, size_t max_frames,
                               lphy_ragged_desc* h_desc, lphy_find_info* h_info);
+
+/* ------------------------------------------------------------------------
+ * Channeliser: `channels` narrow-band streams from one wideband capture, a
+ * mixer, a low-pass FIR and a decimator per channel.  No reference function:
+ * the reference, like every call above, starts from a capture that is one LoRa
+ * channel at the context's sample rate.  It stands in front of the chain,
+ *   lphy_hip_channelize -> lphy_hip_detect_batch -> lphy_hip_find_frames -> ...
+ * on the device and in stream order.  Samples are interleaved float32 I/Q.
+ *
+ * With T = taps, D = decim, R = rot_period of *plan, for channel c < channels
+ * and output m < outputs:
+ *     ar = ai = +0.0f
+ *     for k = 0 .. T-1, in this order:
+ *         x = in[first + m*D + k]          g = taps[c*T + k]
+ *         pr = x.re*g.re - x.im*g.im       pi = x.re*g.im + x.im*g.re
+ *         ar = ar + pr                     ai = ai + pi
+ *     r = rot[c*R + (rot_first + m) % R]
+ *     out[c*out_stride + m] = (ar*r.re - ai*r.im,  ar*r.im + ai*r.re)
+ * Every product, sum and difference is one IEEE float32 operation rounded on
+ * its own: no FMA, no reassociation, subnormals kept.  The device computes no
+ * trigonometry: taps (channels x T) and rot (channels x R) are the caller's
+ * complex float32 tables in device memory, so the result is a pure function of
+ * its inputs, the same bits on every run.  In signal terms taps[c] is a
+ * low-pass prototype times channel c's mixer over one filter length and rot[c]
+ * the mixer's phase at the decimated rate, periodic whenever the centre is a
+ * rational number of cycles per sample.  `first` lets the blocks of a long
+ * capture overlap by T - D samples and `rot_first` carries the rotation's
+ * phase from one block to the next.
+ *
+ * Limits: channels 1..64, taps 1..4096, decim 1..65536 (decim > taps is
+ * legal: samples are skipped), rot_period 1..65536, outputs < 2^32,
+ * out_stride >= outputs, in_samples <= 2^48, first + (outputs-1)*decim + taps
+ * <= in_samples (asked with outputs > 0), channels * out_stride <= 2^48.
+ *
+ * Returns, all before any device call and in this order: -EINVAL for a null
+ * ctx, plan, d_taps or d_rot; d_in or d_out null with outputs > 0; d_in,
+ * d_taps, d_rot or d_out not 8-byte aligned; reserved != 0; channels, taps,
+ * decim or rot_period == 0.  -ERANGE, in this order, for channels > 64; taps >
+ * 4096; decim > 65536; rot_period > 65536; outputs >= 2^32; out_stride <
+ * outputs; in_samples > 2^48; a tap outside the capture; channels * out_stride
+ * > 2^48 (each computed without overflow).  outputs == 0 then returns 0 and
+ * launches nothing.
+ *
+ * The device form is asynchronous on `stream`: one launch, no device
+ * allocation, nothing read back, no workgroup waits on another and no atomic.
+ * It writes out[c*out_stride + m] for m < outputs alone: slots outputs ..
+ * out_stride-1 of every channel keep the caller's values.  d_in and d_out must
+ * not overlap; the call does not check it.  Any SF: ctx supplies the device
+ * and, for the host form, the stream and the staging (the host form moves the
+ * samples first .. first + (outputs-1)*decim + taps alone, and all of h_out
+ * both ways).
+ * lphy_hip_channelize_outputs: the largest `outputs` for which every tap lies
+ * inside the capture, 0 when there is none (or taps or decim is 0).
+ * --------------------------------------------------------------------- */
+typedef struct lphy_chan_plan {   /* host memory, read on the host */
+    uint64_t first;          /* input sample of output 0's first tap                    */
+    uint64_t in_samples;     /* the capture's length in samples                         */
+    uint64_t outputs;        /* outputs per channel                                     */
+    uint64_t out_stride;     /* samples between the channels' streams in out            */
+    uint64_t rot_first;      /* rotation phase of output 0: rot[c*R + rot_first % R]    */
+    uint32_t channels, taps, decim, rot_period;
+    uint32_t reserved[2];    /* 0 */
+} lphy_chan_plan;
+
+uint64_t lphy_hip_channelize_outputs(uint64_t in_samples, uint64_t first,
+                                     uint32_t taps, uint32_t decim);   /* host-only */
+int lphy_hip_channelize(lphy_hip_ctx* ctx, const float* d_in, const lphy_chan_plan* plan,
+                        const float* d_taps, const float* d_rot, float* d_out, void* stream);
+int lphy_hip_channelize_host(lphy_hip_ctx* ctx, const float* h_in, const lphy_chan_plan* plan,
+                             const float* h_taps, const float* h_rot, float* h_out);
 
 /* Hamming(8,4)sx decode + sx1272 CRC of device symbols: frame f holds
  * syms_per_frame symbols at d_syms + f*syms_per_frame and yields

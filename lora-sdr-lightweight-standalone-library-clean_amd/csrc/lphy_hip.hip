@@ -4,7 +4,8 @@
 // the kernels templated on SF are the lphy_sf.hip objects'), and the
 // SF-independent kernels themselves: the finalisation (k_finalize), the
 // modulator and the compensation (lphy_mod.h), the ragged transmit path
-// (lphy_tx.h), the frame search (lphy_find.h), k_mark_recheck.  The host-
+// (lphy_tx.h), the frame search (lphy_find.h), the channeliser (lphy_chan.h),
+// k_mark_recheck.  The host-
 // buffer forms (*_host) are lphy_host.h, included at the end.
 #include "lphy_args.h"
 #include "lphy_final.h"
@@ -14,6 +15,7 @@
 #include "lphy_stage_plan.h"
 #include "lphy_lorawan_ragged.h"
 #include "lphy_find.h"
+#include "lphy_chan.h"
 #include "lphy_testing.h"
 
 #include <climits>
@@ -716,6 +718,34 @@ int lphy_hip_find_frames(lphy_hip_ctx* c, const lphy_detect_rec* d_rec, size_t w
                                    d_work && ((uintptr_t)d_work & 15) == 0))
         return rc;
     return find_frames_impl(c, d_rec, windows, *p, mode, max_frames, d_desc, d_info, d_work, (hipStream_t)stream);
+}
+
+// ---- the channeliser (lphy_chan.h) -------------------------------------------
+uint64_t lphy_hip_channelize_outputs(uint64_t in_samples, uint64_t first, uint32_t taps, uint32_t decim) {
+    return chan_outputs(in_samples, first, taps, decim);
+}
+
+namespace {
+int channelize_check(const lphy_hip_ctx* c, const float* in, const lphy_chan_plan* p, const float* taps,
+                     const float* rot, const float* out) {
+    return chan_args(c != nullptr, p, taps && rot, in != nullptr, out != nullptr, chan_aligned(in, taps, rot, out));
+}
+
+// The one launch; the plan has passed channelize_check and has outputs > 0.
+int channelize_impl(lphy_hip_ctx* c, const float* d_in, const lphy_chan_plan& p, const float* d_taps,
+                    const float* d_rot, float* d_out, hipStream_t st) {
+    HIP_OK(hipSetDevice(c->device));
+    chan_launch(p, d_in, d_taps, d_rot, d_out, st);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+}  // namespace
+
+int lphy_hip_channelize(lphy_hip_ctx* c, const float* d_in, const lphy_chan_plan* p, const float* d_taps,
+                        const float* d_rot, float* d_out, void* stream) {
+    if (int rc = channelize_check(c, d_in, p, d_taps, d_rot, d_out)) return rc;
+    if (p->outputs == 0) return 0;
+    return channelize_impl(c, d_in, *p, d_taps, d_rot, d_out, (hipStream_t)stream);
 }
 
 int lphy_hip_detect_serial_count(lphy_hip_ctx* c, unsigned long long* out, int reset) {

@@ -202,6 +202,25 @@ int lphy_hip_find_frames_host(lphy_hip_ctx* c, const lphy_detect_rec* h_rec, siz
                                       hc.stream()));
 }
 
+// The channeliser on host buffers: the samples its outputs read (from `first`
+// on, so the staged plan starts at 0), the two tables and the caller's output
+// in, the one launch, the output back - all of it, so that the slots no output
+// owns come back as they went.
+int lphy_hip_channelize_host(lphy_hip_ctx* c, const float* h_in, const lphy_chan_plan* p, const float* h_taps,
+                             const float* h_rot, float* h_out) {
+    if (int rc = channelize_check(c, h_in, p, h_taps, h_rot, h_out)) return rc;
+    if (p->outputs == 0) return 0;
+    lphy_chan_plan q = *p;
+    q.in_samples = (p->outputs - 1) * p->decim + p->taps;
+    q.first = 0;
+    HostCall hc(c, kPageable);
+    if (int rc = hc.begin(chan_plan(q.in_samples, p->channels, p->taps, p->rot_period, p->out_stride),
+                          {h_in + 2 * p->first, h_taps, h_rot, h_out}))
+        return rc;
+    return hc.finish(channelize_impl(c, hc.dev<float>(0), q, hc.dev<float>(1), hc.dev<float>(2), hc.dev<float>(3),
+                                     hc.stream()));
+}
+
 int lphy_hip_decode_host(lphy_hip_ctx* c, const uint16_t* h_syms, size_t count,
                          uint8_t* h_bytes, lphy_frame_meta* h_meta) {
     if (!c || !h_syms || !h_bytes || !h_meta) return -EINVAL;

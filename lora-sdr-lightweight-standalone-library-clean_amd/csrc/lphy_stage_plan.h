@@ -163,6 +163,18 @@ inline StagePlan find_plan(size_t windows, size_t max_frames, size_t work_bytes)
         .add(work_bytes, kStageScratch);
 }
 
+// samples (those the outputs read) | taps | rot | out (all channels' strides;
+// the caller's values go in, so that the slots past `outputs` come back as they
+// went) - lphy_hip_channelize_host.  Like find_plan not among the plans
+// lphy_hip_ctx_reserve sizes for: a wideband capture is not a frame shape.
+inline StagePlan chan_plan(size_t samples, size_t channels, size_t taps, size_t rot_period, size_t out_stride) {
+    return StagePlan()
+        .add(samples * kIqBytes, kStageIn)
+        .add(channels * taps * kIqBytes, kStageIn)
+        .add(channels * rot_period * kIqBytes, kStageIn)
+        .add(channels * out_stride * kIqBytes, kStageInOut);
+}
+
 // Staging every *_host entry point needs for calls of up to `frames` frames
 // of `frame_samples` samples, or one buffer of frames * frame_samples: the
 // largest of the eleven plans at that shape (the ragged estimate's slices are

@@ -111,6 +111,61 @@ def find_params(first=0, hop=0, lead=0, total_samples=0, threshold_db=0.0, max_g
     p[0] = (first, hop, lead, total_samples, threshold_db, max_gap, min_symbols, reserved)
     return p
 
+# lphy_chan_plan (include/lphy_hip.h): the channeliser
+CHAN_PLAN = np.dtype([("first", "<u8"), ("in_samples", "<u8"), ("outputs", "<u8"), ("out_stride", "<u8"),
+                      ("rot_first", "<u8"), ("channels", "<u4"), ("taps", "<u4"), ("decim", "<u4"),
+                      ("rot_period", "<u4"), ("reserved", "<u4", (2,))])
+assert CHAN_PLAN.itemsize == 64
+CHAN_TILE = 256  # outputs of every channel per workgroup (csrc/lphy_chan_plan.h kChanTile)
+
+
+def chan_plan(first=0, in_samples=0, outputs=0, out_stride=0, rot_first=0, channels=0, taps=0, decim=0,
+              rot_period=0, reserved=(0, 0)) -> np.ndarray:
+    """One CHAN_PLAN record."""
+    p = np.zeros(1, CHAN_PLAN)
+    p[0] = (first, in_samples, outputs, out_stride, rot_first, channels, taps, decim, rot_period, reserved)
+    return p
+
+
+def channelize_outputs(in_samples: int, first: int, taps: int, decim: int) -> int:
+    """The largest `outputs` for which every tap lies inside a capture of
+    in_samples (lphy_hip_channelize_outputs); 0 when there is none."""
+    return int(load().lphy_hip_channelize_outputs(in_samples, first, taps, decim))
+
+
+def chan_design(centres, decim: int, taps: int, cutoff: float, beta: float):
+    """Tables for lphy_hip_channelize from channel centres: `centres` are
+    fractions.Fraction cycles per input sample, `cutoff` the low-pass edge in
+    cycles per input sample.  Returns (taps complex64 [C, T], rot complex64
+    [C, R], R, delay): channel c is the input times exp(-2 pi i centre n),
+    through a Kaiser(beta)-windowed sinc of `taps` coefficients with unit gain
+    at DC, every `decim`-th sample; delay = (taps - 1) / 2 input samples.  The
+    phases are reduced exactly (Fraction arithmetic), everything else is
+    float64, rounded to float32 once.  R is the least common period of
+    centre * decim; ValueError when it exceeds 65536."""
+    import math
+    from fractions import Fraction
+    cs = [Fraction(c) for c in centres]
+    if not cs or taps < 1 or decim < 1:
+        raise ValueError("chan_design: at least one centre, one tap and decim >= 1")
+    R = 1
+    for c in cs:
+        R = math.lcm(R, (c * decim).denominator)
+    if R > 65536:
+        raise ValueError(f"chan_design: rotation period {R} exceeds 65536")
+    k = np.arange(taps, dtype=np.float64)
+    h = 2.0 * cutoff * np.sinc(2.0 * cutoff * (k - (taps - 1) / 2.0)) * np.kaiser(taps, beta)
+    h = h / h.sum()
+    t = np.empty((len(cs), taps), np.complex128)
+    r = np.empty((len(cs), R), np.complex128)
+    for i, c in enumerate(cs):
+        pt = 2.0 * np.pi * np.array([float((c * n) % 1) for n in range(taps)])
+        pr = 2.0 * np.pi * np.array([float((c * decim * n) % 1) for n in range(R)])
+        t[i] = h * (np.cos(pt) - 1j * np.sin(pt))
+        r[i] = np.cos(pr) - 1j * np.sin(pr)
+    return t.astype(np.complex64), r.astype(np.complex64), R, (taps - 1) / 2.0
+
+
 _vp = C.c_void_p
 _sz = C.c_size_t
 
@@ -133,6 +188,7 @@ EXPORTS = (
     "lphy_hip_estimate_ragged", "lphy_hip_estimate_ragged_host",
     "lphy_hip_detect_ragged", "lphy_hip_detect_ragged_host",
     "lphy_hip_find_frames_workspace", "lphy_hip_find_frames", "lphy_hip_find_frames_host",
+    "lphy_hip_channelize_outputs", "lphy_hip_channelize", "lphy_hip_channelize_host",
     "lphy_hip_symbol_samples", "lphy_hip_lorawan_build_ragged", "lphy_hip_lorawan_tx_layout",
     "lphy_hip_lorawan_parse_ragged", "lphy_hip_lorawan_sessions_check",
     "lphy_hip_lorawan_crypt_batch", "lphy_hip_lorawan_crypt_tx_ragged", "lphy_hip_lorawan_crypt_rx_ragged",
@@ -202,6 +258,10 @@ def load(path: Path | None = None) -> C.CDLL:
     L.lphy_hip_find_frames_workspace.restype = _sz
     L.lphy_hip_find_frames.argtypes = [_vp, _vp, _sz, _vp, C.c_int, _sz, _vp, _vp, _vp, _vp]
     L.lphy_hip_find_frames_host.argtypes = [_vp, _vp, _sz, _vp, C.c_int, _sz, _vp, _vp]
+    L.lphy_hip_channelize_outputs.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32]
+    L.lphy_hip_channelize_outputs.restype = C.c_uint64
+    L.lphy_hip_channelize.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp]
+    L.lphy_hip_channelize_host.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp]
     L.lphy_hip_decode_batch.argtypes = [_vp, _vp, _sz, _sz, _vp, _vp, _vp]
     L.lphy_hip_estimate_batch.argtypes = [_vp, _vp, _sz, _sz, _sz, _vp, _vp]
     L.lphy_hip_estimate_ragged.argtypes = [_vp, _vp, _vp, _sz, _sz, _vp, _vp]
@@ -519,6 +579,58 @@ class Demodulator:
                                                 prm.ctypes.data, mode, max_frames, desc.ctypes.data,
                                                 info.ctypes.data), "lphy_hip_find_frames_host")
         return desc, info[0]
+
+    # --- the channeliser (lphy_hip_channelize*) --------------------------
+    def channelize(self, iq, plan, taps, rot, out, stream=None):
+        """`channels` mixed, filtered and decimated streams from one wideband
+        capture (lphy_hip_channelize): out[c*out_stride + m] = rot[c, (rot_first
+        + m) % R] * sum_k iq[first + m*decim + k] * taps[c, k], every operation
+        a float32 one in the header's order.  `plan`: one CHAN_PLAN record
+        (chan_plan()); `iq`: device tensor of in_samples complex samples;
+        `taps`, `rot`: device tensors of channels x taps and channels x
+        rot_period complex samples (chan_design()); `out`: device tensor of
+        channels x out_stride complex samples, of which the call writes the
+        first `outputs` of every channel.  Asynchronous."""
+        dv = self.device
+        p = np.ascontiguousarray(plan, CHAN_PLAN).reshape(-1)
+        if p.size != 1:
+            raise ValueError(f"plan: one CHAN_PLAN record expected, got {p.size}")
+        q = p[0]
+        ch = int(q["channels"])
+        p_in = _dev_buf(iq, "iq", dv, int(q["in_samples"]) * 8, None)
+        p_taps = _dev_buf(taps, "taps", dv, ch * int(q["taps"]) * 8, None)
+        p_rot = _dev_buf(rot, "rot", dv, ch * int(q["rot_period"]) * 8, None)
+        p_out = _dev_buf(out, "out", dv, ch * int(q["out_stride"]) * 8, None)
+        _chk(self.lib.lphy_hip_channelize(self.ctx, p_in, p.ctypes.data, p_taps, p_rot, p_out, stream),
+             "lphy_hip_channelize")
+
+    def channelize_host(self, iq: np.ndarray, taps: np.ndarray, rot: np.ndarray, decim: int, first: int = 0,
+                        outputs: int | None = None, rot_first: int = 0, out: np.ndarray | None = None) -> np.ndarray:
+        """The same on host arrays: `taps` [channels, T] and `rot` [channels, R]
+        complex64; `outputs` defaults to all the capture holds from `first`
+        (channelize_outputs).  `out`, when given, is a C-contiguous complex64
+        [channels, out_stride] array whose columns past `outputs` the call
+        leaves alone.  Returns the (channels, outputs) complex64 result (a view
+        of `out` when given)."""
+        x = np.ascontiguousarray(iq, np.complex64).reshape(-1)
+        t = np.ascontiguousarray(taps, np.complex64)
+        r = np.ascontiguousarray(rot, np.complex64)
+        if t.ndim != 2 or r.ndim != 2 or t.shape[0] != r.shape[0]:
+            raise ValueError(f"taps {t.shape} and rot {r.shape}: [channels, T] and [channels, R] expected")
+        if outputs is None:
+            outputs = channelize_outputs(x.size, first, t.shape[1], decim)
+        if out is None:
+            out = np.zeros((t.shape[0], outputs), np.complex64)
+        if (out.dtype != np.complex64 or out.ndim != 2 or not out.flags.c_contiguous or out.shape[0] != t.shape[0]
+                or out.shape[1] < outputs):
+            raise ValueError(f"out: C-contiguous complex64 [{t.shape[0]}, >= {outputs}] expected")
+        p = chan_plan(first, x.size, outputs, out.shape[1], rot_first, t.shape[0], t.shape[1], decim, r.shape[1])
+        pad = np.zeros(1, np.complex64)
+        _chk(self.lib.lphy_hip_channelize_host(self.ctx, (x if x.size else pad).ctypes.data, p.ctypes.data,
+                                               (t if t.size else pad).ctypes.data, (r if r.size else pad).ctypes.data,
+                                               (out if out.size else pad).ctypes.data),
+             "lphy_hip_channelize_host")
+        return out[:, :outputs]
 
     def detect_serial_count(self, reset: bool = True) -> int:
         """Windows whose power_avg took the in-order walk of the bins because
