@@ -818,7 +818,11 @@ int lphy_hip_bounds_violations(lphy_hip_ctx* ctx, unsigned long long* out, int r
  * Batch forms of the codec helpers of the reference's LoRaCodes.hpp (SURVEY
  * §8f rank 3) on device buffers; `stream` is a hipStream_t (NULL = default).
  * Rows are `frames` records `stride` elements apart.  Results equal the
- * reference helper applied to each row (tests/test_gpu_codes.py).
+ * reference helper applied to each row (tests/test_gpu_codes.py); elements
+ * past a row's length, or past its last whole interleaver block, are left
+ * alone.  Each call returns 0, -EINVAL or -ERANGE as stated with it, or -EIO
+ * when the launch failed.  With frames (or count) zero an otherwise valid
+ * call returns 0, null buffers included, and nothing is launched.
  * --------------------------------------------------------------------- */
 enum lphy_whiten_kind {
     LPHY_WHITEN_SX1232 = 0,      /* SX1232RadioComputeWhitening (LoRaCodes.hpp:111-137) */
@@ -842,40 +846,55 @@ enum lphy_sum_kind {
 };
 
 /* binaryToGray16 (to_binary = 0) / grayToBinary16 (1), in place
- * (LoRaCodes.hpp:201-222). */
+ * (LoRaCodes.hpp:201-222).  -EINVAL for a null buffer with count > 0. */
 int lphy_hip_gray_batch(uint16_t* d_syms, size_t count, int to_binary, void* stream);
 
 /* diagonalInterleaveSx (LoRaCodes.hpp:376-393) per row: cw_per_frame / ppm
- * blocks of ppm codewords -> (4 + rdd) symbols each.  -ERANGE when a row's
- * symbols exceed sym_stride.  1 <= ppm <= 16, rdd <= 4. */
+ * blocks of ppm codewords -> (4 + rdd) symbols each; codeword bits at and
+ * above 4 + rdd are ignored, as are the codewords after the last whole block.
+ * 1 <= ppm <= 16, rdd <= 4: -EINVAL otherwise, and for a null buffer with
+ * frames > 0.  -ERANGE when a row's symbols exceed sym_stride or
+ * cw_per_frame exceeds cw_stride. */
 int lphy_hip_interleave_batch(const uint8_t* d_cw, size_t frames, size_t cw_stride, size_t cw_per_frame,
                               uint16_t* d_syms, size_t sym_stride, unsigned ppm, unsigned rdd,
                               void* stream);
 
 /* diagonalDeterleaveSx (LoRaCodes.hpp:396-412) per row: syms_per_frame /
  * (4 + rdd) blocks -> ppm codewords each, written as the reference leaves a
- * zero-initialised codeword buffer. */
+ * zero-initialised codeword buffer; symbol bits at and above ppm are ignored.
+ * -EINVAL as for the interleaver; -ERANGE when a row's codewords exceed
+ * cw_stride or syms_per_frame exceeds sym_stride. */
 int lphy_hip_deinterleave_batch(const uint16_t* d_syms, size_t frames, size_t sym_stride,
                                 size_t syms_per_frame, uint8_t* d_cw, size_t cw_stride, unsigned ppm,
                                 unsigned rdd, void* stream);
 
 /* Whitening / de-whitening of the first `len` bytes of every row in place
  * (the generators are involutions).  bit_ofs and rdd as the reference's
- * bitOfs / RDD (ignored by LPHY_WHITEN_SX1232). */
+ * bitOfs / RDD (ignored by LPHY_WHITEN_SX1232).  Any bit_ofs in
+ * [0, INT_MAX] is accepted and the cost does not depend on it: the
+ * generators are periodic and the offset is reduced by the period
+ * (csrc/lphy_codes_plan.h).  -EINVAL for an unknown kind, rdd > 4 (the
+ * SX1272 kinds), bit_ofs < 0, len > 65535, len > stride or a null buffer
+ * with work to do. */
 int lphy_hip_whiten_batch(uint8_t* d_bytes, size_t frames, size_t stride, size_t len, int kind,
                           int bit_ofs, unsigned rdd, void* stream);
 
 /* Hamming / parity code `op` on `count` bytes in place; the decoders' error
- * flags go to d_flags[i] when it is not NULL. */
+ * flags go to d_flags[i] when it is not NULL.  -EINVAL for an op that is
+ * no lphy_code_op or a null d_bytes with count > 0. */
 int lphy_hip_hamming_batch(uint8_t* d_bytes, size_t count, int op, uint8_t* d_flags, void* stream);
 
-/* Checksum `kind` of every row -> d_out[frame] (uint16). */
+/* Checksum `kind` of every row -> d_out[frame] (uint16).  LPHY_SUM_HEADER
+ * ignores `len` and reads 2 bytes a row.  -EINVAL for an unknown kind, more
+ * bytes a row than stride (len, or 2 for the header), or a null buffer with
+ * frames > 0. */
 int lphy_hip_checksum_batch(const uint8_t* d_bytes, size_t frames, size_t stride, size_t len, int kind,
                             uint16_t* d_out, void* stream);
 
 /* lora_encode (LoRaEncoder.cpp:6-18) per row: byte j of the first `len`
  * bytes -> symbols 2j, 2j+1 (encodeHamming84sx of the high, low nibble),
- * the symbols modulate_batch takes.  -ERANGE when 2*len > sym_stride. */
+ * the symbols modulate_batch takes.  -EINVAL when len > stride or a buffer
+ * is null with frames and len > 0; -ERANGE when 2*len > sym_stride. */
 int lphy_hip_lora_encode_batch(const uint8_t* d_bytes, size_t frames, size_t stride, size_t len,
                                uint16_t* d_syms, size_t sym_stride, void* stream);
 

@@ -4,7 +4,10 @@
 // codes and the checksums, over `frames` rows of a fixed stride in device
 // memory.  Each kernel cites the helper whose results it reproduces bit for
 // bit (tests/test_gpu_codes.py against the oracle, which
-// tests/test_oracle_vs_reference.py pins to the reference header).
+// tests/test_oracle_vs_reference.py pins to the reference header).  The
+// whitening generators and their reduction by the period are in
+// lphy_codes_plan.h, which tests/cpp/codes_plan_check.cpp
+// (tests/test_codes_plan_cpu.py) checks on the CPU.
 //
 // All of these are byte/halfword streams: one thread per output element,
 // coalesced along the row; they run at memory speed and need no LDS.
@@ -15,6 +18,7 @@
 #include <cstdio>
 
 #include "../../include/lphy_hip.h"
+#include "lphy_codes_plan.h"
 
 namespace {
 
@@ -102,43 +106,20 @@ __global__ void k_deinterleave(const uint16_t* sy, unsigned long long sy_stride,
 //   LPHY_WHITEN_SX1272       Sx1272ComputeWhitening (:147-167): stored 510-bit sequence
 //   LPHY_WHITEN_SX1272_LFSR  Sx1272ComputeWhiteningLfsr (:176-189): two interleaved
 //                            64-bit LFSR states, one step per codeword
-__constant__ unsigned long long c_whiten_seq[8] = {
-    0x0102291EA751AAFFull, 0xD24B050A8D643A17ull, 0x5B279B671120B8F4ull, 0x032B37B9F6FB55A2ull,
-    0x994E0F87E95E2D16ull, 0x7CBCFC7631984C26ull, 0x281C8E4F0DAEF7F9ull, 0x1741886EB7733B15ull};
-__constant__ int c_whiten_ofs[8] = {6, 4, 2, 0, -112, -114, -302, -34};
-__constant__ int c_whiten_ofs1[5] = {6, 4, 2, 0, -360};
+__constant__ unsigned long long c_whiten_seq[8] = LPHY_WHITEN_SEQ_INIT;
+__constant__ int c_whiten_ofs[8] = LPHY_WHITEN_TAPS_INIT;
+__constant__ int c_whiten_ofs1[5] = LPHY_WHITEN_TAPS_CR1_INIT;
 
-__device__ __forceinline__ unsigned long long lfsr64_step(unsigned long long r) {
-    return (r >> 8) | (((r >> 32) ^ (r >> 24) ^ (r >> 16) ^ r) << 56);  // poly 0x1D
-}
-
+// `ofs` is the entry point's whiten_reduce_ofs(kind, bit_ofs) < 510; the mask
+// (lphy_codes_plan.h: whiten_mask) costs at most one period of steps,
+// whatever bit_ofs and j are.
 __global__ void k_whiten(uint8_t* b, unsigned long long stride, unsigned long long frames, unsigned len,
-                         int kind, int bit_ofs, unsigned rdd) {
+                         int kind, unsigned ofs, unsigned rdd) {
     const unsigned long long t = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= frames * len) return;
     const unsigned long long f = t / len;
     const unsigned j = (unsigned)(t - f * len);
-    unsigned mask = 0;
-    if (kind == LPHY_WHITEN_SX1232) {
-        unsigned s = 0x1FF;
-        for (unsigned k = 0; k < 8u * j; ++k) s = (s >> 1) | (((s ^ (s >> 5)) & 1u) << 8);
-        mask = s & 0xFF;
-    } else if (kind == LPHY_WHITEN_SX1272) {
-        const int* ofs = rdd == 1 ? c_whiten_ofs1 : c_whiten_ofs;
-        for (unsigned i = 0; i < 4 + rdd; ++i) {
-            const int q = (ofs[i] + (int)j + bit_ofs + 510) % 510;
-            mask |= (unsigned)((c_whiten_seq[q >> 6] >> (q & 63)) & 1ull) << i;
-        }
-        mask &= 0xFF;
-    } else {
-        // codeword position p = bit_ofs + j uses state p & 1 after p >> 1 steps
-        const bool one = rdd == 1;
-        const unsigned p = (unsigned)bit_ofs + j;
-        unsigned long long r = (p & 1u) ? (one ? 0xF8ECFEEFEFEFEFEFull : 0xE85C2EFFFFFFFFFFull)
-                                        : (one ? 0x05121100F8ECFEEFull : 0x6572D100E85C2EFFull);
-        for (unsigned k = 0; k < (p >> 1); ++k) r = lfsr64_step(r);
-        mask = (unsigned)(r & (0xffu >> (4 - rdd)));
-    }
+    const unsigned mask = lphy::whiten_mask(kind, ofs, j, rdd, c_whiten_seq, rdd == 1 ? c_whiten_ofs1 : c_whiten_ofs);
     b[f * stride + j] ^= (uint8_t)mask;
 }
 
@@ -340,7 +321,7 @@ int lphy_hip_whiten_batch(uint8_t* d_bytes, size_t frames, size_t stride, size_t
     if (!frames || !len) return 0;
     hipLaunchKernelGGL(k_whiten, dim3(blocks_for(frames * len)), dim3(kThreads), 0, (hipStream_t)stream,
                        d_bytes, (unsigned long long)stride, (unsigned long long)frames, (unsigned)len, kind,
-                       bit_ofs, rdd);
+                       lphy::whiten_reduce_ofs(kind, bit_ofs), rdd);
     CODES_OK(hipGetLastError());
     return 0;
 }

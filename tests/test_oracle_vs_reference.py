@@ -372,3 +372,44 @@ def test_codes_whitening_and_checksums(oracle, reference, kind):
     # whitening_test.cpp:30-31 known answer
     w = oracle.whiten(np.frombuffer(bytes.fromhex("DEADBEEF700D"), np.uint8), 2, 0, 4)
     assert w.tobytes() == bytes.fromhex("215290102CF2")
+
+
+# ---- the parameters tests/test_gpu_codes.py leans on the oracle for beyond the
+# SX127x geometries above: every ppm 1..16 (ppm < 4 + rdd, where the diagonal
+# wraps more than once, and 13..16 among them) and rdd 0..4, on inputs with
+# every bit set at random: codeword bits at and above 4 + rdd and symbol bits
+# at and above ppm, which both sides must ignore.
+@pytest.mark.parametrize("rdd", range(5))
+def test_codes_interleaver_every_geometry_full_width(oracle, reference, rdd):
+    rng = np.random.default_rng(900 + rdd)
+    nb = 4 + rdd
+    for ppm in range(1, 17):
+        cw = rng.integers(0, 256, 3 * ppm + (ppm - 1), dtype=np.uint8)
+        a, b = oracle.interleave(cw, ppm, rdd), reference.interleave(cw, ppm, rdd)
+        assert len(a) == 3 * nb
+        np.testing.assert_array_equal(a, b, str(ppm))
+        np.testing.assert_array_equal(a, oracle.interleave(cw & ((1 << nb) - 1), ppm, rdd))
+        syms = rng.integers(0, 65536, 3 * nb + (nb - 1), dtype=np.uint16)
+        c, d = oracle.deinterleave(syms, ppm, rdd), reference.deinterleave(syms, ppm, rdd)
+        assert len(c) == 3 * ppm
+        np.testing.assert_array_equal(c, d, str(ppm))
+        np.testing.assert_array_equal(c, oracle.deinterleave(syms & ((1 << ppm) - 1), ppm, rdd))
+        np.testing.assert_array_equal(oracle.deinterleave(a, ppm, rdd), cw[: 3 * ppm] & ((1 << nb) - 1))
+
+
+@pytest.mark.parametrize("kind", [0, 1, 2])
+def test_codes_whitening_across_periods(oracle, reference, kind):
+    """Rows of 600 and 1024 full-width bytes from offsets at, around and several
+    times past the generators' period of 510 positions, every rdd; and the
+    longest row the reference's uint16_t length admits."""
+    rng = np.random.default_rng(920 + kind)
+    for rdd in range(5):
+        for bit_ofs in (0, 1, 3, 100, 503, 504, 509, 510, 511, 1019, 1020, 1021, 5103):
+            for n in (600, 1024):
+                buf = rng.integers(0, 256, n, dtype=np.uint8)
+                a, b = oracle.whiten(buf, kind, bit_ofs, rdd), reference.whiten(buf, kind, bit_ofs, rdd)
+                np.testing.assert_array_equal(a, b, str((rdd, bit_ofs, n)))
+                if kind:  # only the 4 + rdd codeword bits change
+                    assert not ((a ^ buf) & (0xFF ^ (0xFF >> (4 - rdd)))).any()
+    buf = rng.integers(0, 256, 65535, dtype=np.uint8)
+    np.testing.assert_array_equal(oracle.whiten(buf, kind, 9, 2), reference.whiten(buf, kind, 9, 2))
