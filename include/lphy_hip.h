@@ -32,6 +32,8 @@
  *                          frames found in a capture, from those records
  *   lphy_hip_channelize    no reference function: a wideband capture to the
  *                          per-channel streams the calls above take
+ *   lphy_hip_synthesize    no reference function: per-channel streams (those
+ *                          lphy_hip_tx_ragged makes) to one wideband stream
  *   lphy_hip_decode_batch  lora_phy::decode / lora_decode on device symbols
  *   lphy_hip_estimate_batch lora_phy::estimate_offsets src/phy/phy.cpp:81-148
  *   lphy_hip_estimate_ragged the same for frames of different lengths in one
@@ -516,6 +518,89 @@ uint64_t lphy_hip_channelize_outputs(uint64_t in_samples, uint64_t first,
 int lphy_hip_channelize(lphy_hip_ctx* ctx, const float* d_in, const lphy_chan_plan* plan,
                         const float* d_taps, const float* d_rot, float* d_out, void* stream);
 int lphy_hip_channelize_host(lphy_hip_ctx* ctx, const float* h_in, const lphy_chan_plan* plan,
+                             const float* h_taps, const float* h_rot, float* h_out);
+
+/* ------------------------------------------------------------------------
+ * Synthesiser: one wideband stream from `channels` narrow-band streams, the
+ * channeliser's mirror: per channel a rotation, a polyphase interpolating FIR
+ * and a mixer, then the sum over the channels.  No reference function.  It
+ * stands behind the transmit chain,
+ *   lphy_hip_lorawan_crypt_tx_ragged -> lphy_hip_lorawan_build_ragged ->
+ *   lphy_hip_tx_ragged (one stream per channel) -> lphy_hip_synthesize
+ * on the device and in stream order.  Samples are interleaved float32 I/Q.
+ *
+ * With T = taps, U = interp, R = rot_period of *plan, for output n < outputs
+ * let w = first + n, q = w / U and p = w % U (64-bit integer division and
+ * remainder):
+ *     yr = yi = +0.0f
+ *     for c = 0 .. channels-1, in this order:
+ *         ar = ai = +0.0f
+ *         for i = 0, 1, 2, ... while k = i*U + p < T, in this order:
+ *             j = q - i                                  (signed)
+ *             if 0 <= j < in_samples:
+ *                 x = in[c*in_stride + j]    r = rot[c*R + (rot_first + j) % R]
+ *                 xr = x.re*r.re - x.im*r.im             xi = x.re*r.im + x.im*r.re
+ *             else:
+ *                 xr = xi = +0.0f            (the operand is +0; the products below are still formed)
+ *             g  = taps[c*T + k]
+ *             pr = xr*g.re - xi*g.im                     pi = xr*g.im + xi*g.re
+ *             ar = ar + pr                               ai = ai + pi
+ *         yr = yr + ar                                   yi = yi + ai
+ *     out[n] = (yr, yi)
+ * Every product, sum and difference is one IEEE float32 operation rounded on
+ * its own: no FMA, no reassociation, subnormals kept (the channeliser's rule).
+ * A phase p >= T has no taps: its output is (+0, +0).  The device computes no
+ * trigonometry: taps (channels x T) and rot (channels x R) are the caller's
+ * complex float32 tables in device memory.  In signal terms taps[c] is U times
+ * a low-pass prototype times channel c's mixer exp(+2 pi i f_c k) over one
+ * filter length and rot[c][j] = exp(+2 pi i f_c U j) the mixer's phase at the
+ * narrow rate: the conjugates of the channeliser's tables for decim = U, the
+ * taps scaled by U.  `first` and `rot_first` let a long transmission go out in
+ * blocks: advance d_in by J0 narrow samples, pass first = w0 - J0*U and
+ * rot_first = J0, and the block's bytes are those one call over the whole
+ * transmission gives.
+ *
+ * Limits: channels 1..64, taps 1..4096, interp 1..65536, rot_period 1..65536,
+ * outputs < 2^32, in_stride >= in_samples, in_samples <= 2^48, channels *
+ * in_stride <= 2^48, first + outputs <= 2^48.
+ *
+ * Returns, all before any device call and in this order: -EINVAL for a null
+ * ctx, plan, d_taps or d_rot; d_out null with outputs > 0; d_in null with
+ * outputs > 0 and in_samples > 0; d_in, d_taps, d_rot or d_out (those given)
+ * not 8-byte aligned; reserved != 0; channels, taps, interp or rot_period ==
+ * 0.  -ERANGE, in this order, for channels > 64; taps > 4096; interp > 65536;
+ * rot_period > 65536; outputs >= 2^32; in_stride < in_samples; in_samples >
+ * 2^48; channels * in_stride > 2^48; first + outputs > 2^48 (each computed
+ * without overflow).  outputs == 0 then returns 0 and launches nothing.
+ *
+ * The device form is asynchronous on `stream`: one launch, no device
+ * allocation, nothing read back, no workgroup waits on another and no atomic.
+ * It writes out[0 .. outputs) alone.  d_in and d_out must not overlap; the
+ * call does not check it.  Any SF: ctx supplies the device and, for the host
+ * form, the stream and the staging (the host form moves h_in from channel 0's
+ * first sample to the last channel's sample in_samples - 1, strides included,
+ * and `outputs` samples back).
+ * lphy_hip_synthesize_outputs: the outputs up to the last one an input sample
+ * reaches, (in_samples - 1) * interp + taps - first when in_samples >= 1 and
+ * that is positive, else 0 (also when taps or interp is 0); past the limits
+ * above the product saturates at 2^64 - 1.  A larger `outputs` is legal: the
+ * tail is (+0, +0).
+ * --------------------------------------------------------------------- */
+typedef struct lphy_synth_plan {  /* host memory, read on the host */
+    uint64_t first;          /* wideband sample index of output 0                       */
+    uint64_t in_samples;     /* narrow samples per channel                              */
+    uint64_t in_stride;      /* samples between the channels' streams in in             */
+    uint64_t outputs;        /* wideband samples to write                               */
+    uint64_t rot_first;      /* rotation phase of narrow sample 0: rot[c*R + rot_first % R] */
+    uint32_t channels, taps, interp, rot_period;
+    uint32_t reserved[2];    /* 0 */
+} lphy_synth_plan;
+
+uint64_t lphy_hip_synthesize_outputs(uint64_t in_samples, uint64_t first,
+                                     uint32_t taps, uint32_t interp);   /* host-only */
+int lphy_hip_synthesize(lphy_hip_ctx* ctx, const float* d_in, const lphy_synth_plan* plan,
+                        const float* d_taps, const float* d_rot, float* d_out, void* stream);
+int lphy_hip_synthesize_host(lphy_hip_ctx* ctx, const float* h_in, const lphy_synth_plan* plan,
                              const float* h_taps, const float* h_rot, float* h_out);
 
 /* Hamming(8,4)sx decode + sx1272 CRC of device symbols: frame f holds

@@ -5,7 +5,7 @@
 // SF-independent kernels themselves: the finalisation (k_finalize), the
 // modulator and the compensation (lphy_mod.h), the ragged transmit path
 // (lphy_tx.h), the frame search (lphy_find.h), the channeliser (lphy_chan.h),
-// k_mark_recheck.  The host-
+// the synthesiser (lphy_synth.h), k_mark_recheck.  The host-
 // buffer forms (*_host) are lphy_host.h, included at the end.
 #include "lphy_args.h"
 #include "lphy_final.h"
@@ -16,6 +16,7 @@
 #include "lphy_lorawan_ragged.h"
 #include "lphy_find.h"
 #include "lphy_chan.h"
+#include "lphy_synth.h"
 #include "lphy_testing.h"
 
 #include <climits>
@@ -746,6 +747,34 @@ int lphy_hip_channelize(lphy_hip_ctx* c, const float* d_in, const lphy_chan_plan
     if (int rc = channelize_check(c, d_in, p, d_taps, d_rot, d_out)) return rc;
     if (p->outputs == 0) return 0;
     return channelize_impl(c, d_in, *p, d_taps, d_rot, d_out, (hipStream_t)stream);
+}
+
+// ---- the synthesiser (lphy_synth.h) ------------------------------------------
+uint64_t lphy_hip_synthesize_outputs(uint64_t in_samples, uint64_t first, uint32_t taps, uint32_t interp) {
+    return synth_outputs(in_samples, first, taps, interp);
+}
+
+namespace {
+int synthesize_check(const lphy_hip_ctx* c, const float* in, const lphy_synth_plan* p, const float* taps,
+                     const float* rot, const float* out) {
+    return synth_args(c != nullptr, p, taps && rot, in != nullptr, out != nullptr, synth_aligned(in, taps, rot, out));
+}
+
+// The one launch; the plan has passed synthesize_check and has outputs > 0.
+int synthesize_impl(lphy_hip_ctx* c, const float* d_in, const lphy_synth_plan& p, const float* d_taps,
+                    const float* d_rot, float* d_out, hipStream_t st) {
+    HIP_OK(hipSetDevice(c->device));
+    synth_launch(p, d_in, d_taps, d_rot, d_out, st);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+}  // namespace
+
+int lphy_hip_synthesize(lphy_hip_ctx* c, const float* d_in, const lphy_synth_plan* p, const float* d_taps,
+                        const float* d_rot, float* d_out, void* stream) {
+    if (int rc = synthesize_check(c, d_in, p, d_taps, d_rot, d_out)) return rc;
+    if (p->outputs == 0) return 0;
+    return synthesize_impl(c, d_in, *p, d_taps, d_rot, d_out, (hipStream_t)stream);
 }
 
 int lphy_hip_detect_serial_count(lphy_hip_ctx* c, unsigned long long* out, int reset) {

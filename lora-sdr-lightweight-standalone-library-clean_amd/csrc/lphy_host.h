@@ -221,6 +221,22 @@ int lphy_hip_channelize_host(lphy_hip_ctx* c, const float* h_in, const lphy_chan
                                      hc.stream()));
 }
 
+// The synthesiser on host buffers: the channels' streams (from the first
+// channel's first sample to the last channel's last, strides included), the
+// two tables in, the one launch, `outputs` samples back.
+int lphy_hip_synthesize_host(lphy_hip_ctx* c, const float* h_in, const lphy_synth_plan* p, const float* h_taps,
+                             const float* h_rot, float* h_out) {
+    if (int rc = synthesize_check(c, h_in, p, h_taps, h_rot, h_out)) return rc;
+    if (p->outputs == 0) return 0;
+    const size_t in = p->in_samples ? (size_t)((p->channels - 1) * p->in_stride + p->in_samples) : 0;
+    HostCall hc(c, kPageable);
+    if (int rc = hc.begin(synth_plan(in, p->channels, p->taps, p->rot_period, p->outputs),
+                          {h_in, h_taps, h_rot, h_out}))
+        return rc;
+    return hc.finish(synthesize_impl(c, hc.dev<float>(0), *p, hc.dev<float>(1), hc.dev<float>(2), hc.dev<float>(3),
+                                     hc.stream()));
+}
+
 int lphy_hip_decode_host(lphy_hip_ctx* c, const uint16_t* h_syms, size_t count,
                          uint8_t* h_bytes, lphy_frame_meta* h_meta) {
     if (!c || !h_syms || !h_bytes || !h_meta) return -EINVAL;

@@ -175,6 +175,18 @@ inline StagePlan chan_plan(size_t samples, size_t channels, size_t taps, size_t 
         .add(channels * out_stride * kIqBytes, kStageInOut);
 }
 
+// in (the channels' streams, first sample of the first to last sample of the
+// last) | taps | rot | out (`outputs` samples, every one written) -
+// lphy_hip_synthesize_host.  Beside chan_plan, and like it not among the plans
+// lphy_hip_ctx_reserve sizes for.
+inline StagePlan synth_plan(size_t in_samples, size_t channels, size_t taps, size_t rot_period, size_t outputs) {
+    return StagePlan()
+        .add(in_samples * kIqBytes, kStageIn)
+        .add(channels * taps * kIqBytes, kStageIn)
+        .add(channels * rot_period * kIqBytes, kStageIn)
+        .add(outputs * kIqBytes, kStageOut);
+}
+
 // Staging every *_host entry point needs for calls of up to `frames` frames
 // of `frame_samples` samples, or one buffer of frames * frame_samples: the
 // largest of the eleven plans at that shape (the ragged estimate's slices are

@@ -133,6 +133,40 @@ def channelize_outputs(in_samples: int, first: int, taps: int, decim: int) -> in
     return int(load().lphy_hip_channelize_outputs(in_samples, first, taps, decim))
 
 
+def _design_tables(who: str, centres, step: int, taps: int, cutoff: float, beta: float, synth: bool):
+    """What chan_design and synth_design share: the Kaiser(beta)-windowed sinc
+    with unit gain at DC, the exact (Fraction) phase reduction, the period R of
+    centre * step and its limit.  synth: the mixer turns forward, exp(+i ...),
+    and the prototype is scaled by `step`; else backward, unscaled."""
+    import math
+    from fractions import Fraction
+    cs = [Fraction(c) for c in centres]
+    if not cs or taps < 1 or step < 1:
+        raise ValueError(f"{who}: at least one centre, one tap and a step >= 1")
+    R = 1
+    for c in cs:
+        R = math.lcm(R, (c * step).denominator)
+    if R > 65536:
+        raise ValueError(f"{who}: rotation period {R} exceeds 65536")
+    k = np.arange(taps, dtype=np.float64)
+    h = 2.0 * cutoff * np.sinc(2.0 * cutoff * (k - (taps - 1) / 2.0)) * np.kaiser(taps, beta)
+    h = h / h.sum()
+    if synth:
+        h = h * float(step)
+    t = np.empty((len(cs), taps), np.complex128)
+    r = np.empty((len(cs), R), np.complex128)
+    for i, c in enumerate(cs):
+        pt = 2.0 * np.pi * np.array([float((c * n) % 1) for n in range(taps)])
+        pr = 2.0 * np.pi * np.array([float((c * step * n) % 1) for n in range(R)])
+        if synth:
+            t[i] = h * (np.cos(pt) + 1j * np.sin(pt))
+            r[i] = np.cos(pr) + 1j * np.sin(pr)
+        else:
+            t[i] = h * (np.cos(pt) - 1j * np.sin(pt))
+            r[i] = np.cos(pr) - 1j * np.sin(pr)
+    return t.astype(np.complex64), r.astype(np.complex64), R, (taps - 1) / 2.0
+
+
 def chan_design(centres, decim: int, taps: int, cutoff: float, beta: float):
     """Tables for lphy_hip_channelize from channel centres: `centres` are
     fractions.Fraction cycles per input sample, `cutoff` the low-pass edge in
@@ -143,27 +177,48 @@ def chan_design(centres, decim: int, taps: int, cutoff: float, beta: float):
     phases are reduced exactly (Fraction arithmetic), everything else is
     float64, rounded to float32 once.  R is the least common period of
     centre * decim; ValueError when it exceeds 65536."""
-    import math
-    from fractions import Fraction
-    cs = [Fraction(c) for c in centres]
-    if not cs or taps < 1 or decim < 1:
-        raise ValueError("chan_design: at least one centre, one tap and decim >= 1")
-    R = 1
-    for c in cs:
-        R = math.lcm(R, (c * decim).denominator)
-    if R > 65536:
-        raise ValueError(f"chan_design: rotation period {R} exceeds 65536")
-    k = np.arange(taps, dtype=np.float64)
-    h = 2.0 * cutoff * np.sinc(2.0 * cutoff * (k - (taps - 1) / 2.0)) * np.kaiser(taps, beta)
-    h = h / h.sum()
-    t = np.empty((len(cs), taps), np.complex128)
-    r = np.empty((len(cs), R), np.complex128)
-    for i, c in enumerate(cs):
-        pt = 2.0 * np.pi * np.array([float((c * n) % 1) for n in range(taps)])
-        pr = 2.0 * np.pi * np.array([float((c * decim * n) % 1) for n in range(R)])
-        t[i] = h * (np.cos(pt) - 1j * np.sin(pt))
-        r[i] = np.cos(pr) - 1j * np.sin(pr)
-    return t.astype(np.complex64), r.astype(np.complex64), R, (taps - 1) / 2.0
+    return _design_tables("chan_design", centres, decim, taps, cutoff, beta, synth=False)
+
+
+# lphy_synth_plan (include/lphy_hip.h): the synthesiser
+SYNTH_PLAN = np.dtype([("first", "<u8"), ("in_samples", "<u8"), ("in_stride", "<u8"), ("outputs", "<u8"),
+                       ("rot_first", "<u8"), ("channels", "<u4"), ("taps", "<u4"), ("interp", "<u4"),
+                       ("rot_period", "<u4"), ("reserved", "<u4", (2,))])
+assert SYNTH_PLAN.itemsize == 64
+SYNTH_TILE = 256  # wideband outputs per workgroup (csrc/lphy_synth_plan.h kSynthTile)
+
+
+def synth_plan(first=0, in_samples=0, in_stride=0, outputs=0, rot_first=0, channels=0, taps=0, interp=0,
+               rot_period=0, reserved=(0, 0)) -> np.ndarray:
+    """One SYNTH_PLAN record."""
+    p = np.zeros(1, SYNTH_PLAN)
+    p[0] = (first, in_samples, in_stride, outputs, rot_first, channels, taps, interp, rot_period, reserved)
+    return p
+
+
+def synthesize_outputs(in_samples: int, first: int, taps: int, interp: int) -> int:
+    """The outputs from `first` up to the last one an input sample reaches
+    (lphy_hip_synthesize_outputs): (in_samples - 1) * interp + taps - first, 0
+    when that is not positive."""
+    return int(load().lphy_hip_synthesize_outputs(in_samples, first, taps, interp))
+
+
+def synth_design(centres, interp: int, taps: int, cutoff: float, beta: float):
+    """Tables for lphy_hip_synthesize from channel centres, the mirror of
+    chan_design: `centres` are fractions.Fraction cycles per wideband sample,
+    `cutoff` the low-pass edge in cycles per wideband sample.  Returns (taps
+    complex64 [C, T], rot complex64 [C, R], R, delay): channel c's stream is
+    zero-stuffed by `interp`, passed through `interp` times a
+    Kaiser(beta)-windowed sinc of `taps` coefficients with unit gain at DC
+    (unit gain for the stream, that is) and multiplied by exp(+2 pi i centre
+    w); narrow sample j is centred at wideband sample j * interp + delay,
+    delay = (taps - 1) / 2.  taps[c, k] = interp * h[k] * exp(+2 pi i centre
+    k), rot[c, j] = exp(+2 pi i centre interp j): the conjugates of
+    chan_design's for decim = interp, the taps times interp.  The phases are
+    reduced exactly (Fraction arithmetic), everything else is float64, rounded
+    to float32 once.  R is the least common period of centre * interp;
+    ValueError when it exceeds 65536."""
+    return _design_tables("synth_design", centres, interp, taps, cutoff, beta, synth=True)
 
 
 _vp = C.c_void_p
@@ -189,6 +244,7 @@ EXPORTS = (
     "lphy_hip_detect_ragged", "lphy_hip_detect_ragged_host",
     "lphy_hip_find_frames_workspace", "lphy_hip_find_frames", "lphy_hip_find_frames_host",
     "lphy_hip_channelize_outputs", "lphy_hip_channelize", "lphy_hip_channelize_host",
+    "lphy_hip_synthesize_outputs", "lphy_hip_synthesize", "lphy_hip_synthesize_host",
     "lphy_hip_symbol_samples", "lphy_hip_lorawan_build_ragged", "lphy_hip_lorawan_tx_layout",
     "lphy_hip_lorawan_parse_ragged", "lphy_hip_lorawan_sessions_check",
     "lphy_hip_lorawan_crypt_batch", "lphy_hip_lorawan_crypt_tx_ragged", "lphy_hip_lorawan_crypt_rx_ragged",
@@ -262,6 +318,10 @@ def load(path: Path | None = None) -> C.CDLL:
     L.lphy_hip_channelize_outputs.restype = C.c_uint64
     L.lphy_hip_channelize.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp]
     L.lphy_hip_channelize_host.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp]
+    L.lphy_hip_synthesize_outputs.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32]
+    L.lphy_hip_synthesize_outputs.restype = C.c_uint64
+    L.lphy_hip_synthesize.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp]
+    L.lphy_hip_synthesize_host.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp]
     L.lphy_hip_decode_batch.argtypes = [_vp, _vp, _sz, _sz, _vp, _vp, _vp]
     L.lphy_hip_estimate_batch.argtypes = [_vp, _vp, _sz, _sz, _sz, _vp, _vp]
     L.lphy_hip_estimate_ragged.argtypes = [_vp, _vp, _vp, _sz, _sz, _vp, _vp]
@@ -631,6 +691,57 @@ class Demodulator:
                                                (out if out.size else pad).ctypes.data),
              "lphy_hip_channelize_host")
         return out[:, :outputs]
+
+    # --- the synthesiser (lphy_hip_synthesize*) --------------------------
+    def synthesize(self, streams, plan, taps, rot, out, stream=None):
+        """One wideband stream from `channels` narrow ones
+        (lphy_hip_synthesize): out[n] = sum_c sum_i rot[c, (rot_first + j) % R]
+        * streams[c*in_stride + j] * taps[c, i*interp + p] with first + n = q *
+        interp + p and j = q - i, every operation a float32 one in the header's
+        order.  `plan`: one SYNTH_PLAN record (synth_plan()); `streams`: device
+        tensor of channels x in_stride complex samples (the last channel may
+        stop at in_samples), or None when in_samples is 0; `taps`, `rot`:
+        device tensors of channels x taps and channels x rot_period complex
+        samples (synth_design()); `out`: device tensor of `outputs` complex
+        samples.  Asynchronous."""
+        dv = self.device
+        p = np.ascontiguousarray(plan, SYNTH_PLAN).reshape(-1)
+        if p.size != 1:
+            raise ValueError(f"plan: one SYNTH_PLAN record expected, got {p.size}")
+        q = p[0]
+        ch, n_in = int(q["channels"]), int(q["in_samples"])
+        p_in = None
+        if streams is not None or n_in:
+            p_in = _dev_buf(streams, "streams", dv, ((max(ch, 1) - 1) * int(q["in_stride"]) + n_in) * 8 if n_in else 0,
+                            None)
+        p_taps = _dev_buf(taps, "taps", dv, ch * int(q["taps"]) * 8, None)
+        p_rot = _dev_buf(rot, "rot", dv, ch * int(q["rot_period"]) * 8, None)
+        p_out = _dev_buf(out, "out", dv, int(q["outputs"]) * 8, None)
+        _chk(self.lib.lphy_hip_synthesize(self.ctx, p_in, p.ctypes.data, p_taps, p_rot, p_out, stream),
+             "lphy_hip_synthesize")
+
+    def synthesize_host(self, streams: np.ndarray, taps: np.ndarray, rot: np.ndarray, interp: int, first: int = 0,
+                        rot_first: int = 0, outputs: int | None = None) -> np.ndarray:
+        """The same on host arrays: `streams` [channels, in_samples], `taps`
+        [channels, T] and `rot` [channels, R] complex64; `outputs` defaults to
+        all that an input sample reaches from `first` (synthesize_outputs).
+        Returns the `outputs` complex64 wideband samples."""
+        x = np.ascontiguousarray(streams, np.complex64)
+        t = np.ascontiguousarray(taps, np.complex64)
+        r = np.ascontiguousarray(rot, np.complex64)
+        if x.ndim != 2 or t.ndim != 2 or r.ndim != 2 or not (x.shape[0] == t.shape[0] == r.shape[0]):
+            raise ValueError(f"streams {x.shape}, taps {t.shape} and rot {r.shape}: [channels, in_samples], "
+                             "[channels, T] and [channels, R] expected")
+        if outputs is None:
+            outputs = synthesize_outputs(x.shape[1], first, t.shape[1], interp)
+        out = np.zeros(outputs, np.complex64)
+        p = synth_plan(first, x.shape[1], x.shape[1], outputs, rot_first, t.shape[0], t.shape[1], interp, r.shape[1])
+        pad = np.zeros(1, np.complex64)
+        _chk(self.lib.lphy_hip_synthesize_host(self.ctx, (x if x.size else pad).ctypes.data, p.ctypes.data,
+                                               (t if t.size else pad).ctypes.data, (r if r.size else pad).ctypes.data,
+                                               (out if out.size else pad).ctypes.data),
+             "lphy_hip_synthesize_host")
+        return out
 
     def detect_serial_count(self, reset: bool = True) -> int:
         """Windows whose power_avg took the in-order walk of the bins because

@@ -1,0 +1,262 @@
+"""The synthesiser without a device: the host-compilable part of it
+(csrc/lphy_synth_plan.h: argument check, output count, tile geometry, LDS
+image) as a stand-alone program under ASan + UBSan
+(tests/cpp/synthesize_check.cpp), the binding's constants and record layout
+against the headers, the argument errors from the shared library itself, the
+numpy model of the definition (tests/synthesize_model.py) against tables
+written out by hand, and the design helper lphy.synth_design against the
+model's own float64 maths and against lphy.chan_design."""
+import ctypes
+import errno
+import re
+import subprocess
+from fractions import Fraction as F
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import synthesize_model as model
+
+ROOT = Path(__file__).resolve().parents[1]
+CPP = ROOT / "tests" / "cpp"
+PKG = ROOT / "lora-sdr-lightweight-standalone-library-clean_amd"
+CSRC = PKG / "csrc"
+
+
+@pytest.fixture(scope="module")
+def check_output(tmp_path_factory):
+    exe = tmp_path_factory.mktemp("synthesize") / "synthesize_check"
+    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-fsanitize=address,undefined",
+                        "-fno-sanitize-recover=all", "-I", str(CSRC), "-o", str(exe),
+                        str(CPP / "synthesize_check.cpp")], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    return r.stdout.strip()
+
+
+def test_plan_logic_under_the_host_sanitizers(check_output):
+    assert re.fullmatch(r"synthesize_check: ok kSynthTile=\d+ sizeof\(lphy_synth_plan\)=\d+ offsets=[\d,]+",
+                        check_output), check_output
+
+
+def test_binding_knows_the_tile_and_the_plan(check_output):
+    """lphy.SYNTH_TILE, which the device tests place their edges by, is the
+    header's, and SYNTH_PLAN is lphy_synth_plan as the C compiler lays it out:
+    size and every member's offset."""
+    import lphy
+    text = (CSRC / "lphy_synth_plan.h").read_text()
+    assert int(re.search(r"kSynthTile = (\d+);", text).group(1)) == lphy.SYNTH_TILE
+    tile, size = (int(x) for x in re.findall(r"=(\d+)", check_output)[:2])
+    offsets = [int(x) for x in check_output.rsplit("=", 1)[1].split(",")]
+    assert tile == lphy.SYNTH_TILE and size == lphy.SYNTH_PLAN.itemsize == 64
+    names = ["first", "in_samples", "in_stride", "outputs", "rot_first", "channels", "taps", "interp", "rot_period",
+             "reserved"]
+    assert list(lphy.SYNTH_PLAN.names) == names
+    assert [lphy.SYNTH_PLAN.fields[n][1] for n in names] == offsets
+    p = lphy.synth_plan(first=1, in_samples=2, in_stride=3, outputs=4, rot_first=5, channels=6, taps=7, interp=8,
+                        rot_period=9)
+    assert p.tobytes() == np.array([1, 2, 3, 4, 5], "<u8").tobytes() + np.array([6, 7, 8, 9, 0, 0], "<u4").tobytes()
+
+
+def test_library_refuses_bad_arguments_without_a_device():
+    """The shared library has the three entry points, and the argument check
+    answers before any device call: no context, no device needed."""
+    import lphy
+    L = lphy.load()
+    assert L.lphy_hip_synthesize_outputs(100, 3, 5, 4) == 99 * 4 + 5 - 3
+    assert L.lphy_hip_synthesize_outputs(0, 0, 5, 4) == 0 and L.lphy_hip_synthesize_outputs(1, 5, 5, 4) == 0
+    assert lphy.synthesize_outputs(1 << 48, 0, 4096, 65536) == ((1 << 48) - 1) * 65536 + 4096
+    buf = (ctypes.c_float * 64)()
+    a = ctypes.addressof(buf)
+    p = lphy.synth_plan(0, 4, 4, 8, 0, 1, 5, 2, 3)
+    for fn, tail in ((L.lphy_hip_synthesize, (None,)), (L.lphy_hip_synthesize_host, ())):
+        assert fn(None, a, p.ctypes.data, a, a, a, *tail) == -errno.EINVAL
+        assert fn(None, None, None, None, None, None, *tail) == -errno.EINVAL
+    # with something in the context's place the later rows answer (the context is not
+    # touched before the check has passed, and it never passes here)
+    fake = ctypes.addressof((ctypes.c_char * 8)())
+    d, h = L.lphy_hip_synthesize, L.lphy_hip_synthesize_host
+    assert d(fake, a, None, a, a, a, None) == -errno.EINVAL
+    assert d(fake, a, p.ctypes.data, None, a, a, None) == -errno.EINVAL
+    assert d(fake, a, p.ctypes.data, a, None, a, None) == -errno.EINVAL
+    assert d(fake, a, p.ctypes.data, a, a, None, None) == -errno.EINVAL
+    assert d(fake, None, p.ctypes.data, a, a, a, None) == -errno.EINVAL
+    assert d(fake, a + 4, p.ctypes.data, a, a, a, None) == -errno.EINVAL
+    assert h(fake, a, p.ctypes.data, a, a, a + 4) == -errno.EINVAL
+    bad = p.copy()
+    bad["reserved"][0, 1] = 1
+    assert d(fake, a, bad.ctypes.data, a, a, a, None) == -errno.EINVAL
+    for field in ("channels", "taps", "interp", "rot_period"):
+        bad = p.copy()
+        bad[field] = 0
+        assert d(fake, a, bad.ctypes.data, a, a, a, None) == -errno.EINVAL
+    for field, v in (("channels", 65), ("taps", 4097), ("interp", 65537), ("rot_period", 65537),
+                     ("outputs", 1 << 32), ("in_stride", 3), ("in_samples", (1 << 48) + 1), ("first", (1 << 48) - 7)):
+        bad = p.copy()
+        bad[field] = v
+        if field == "in_samples":
+            bad["in_stride"] = v
+        assert d(fake, a, bad.ctypes.data, a, a, a, None) == -errno.ERANGE, field
+        assert h(fake, a, bad.ctypes.data, a, a, a) == -errno.ERANGE, field
+    bad = p.copy()
+    bad["channels"], bad["in_stride"] = 64, (1 << 42) + 1
+    assert d(fake, a, bad.ctypes.data, a, a, a, None) == -errno.ERANGE
+
+
+def _c(*v):
+    return np.array(v, np.complex64)
+
+
+ONE = _c(1).reshape(1, 1)
+
+
+def test_model_interp_1_is_a_plain_fir():
+    x = _c(1 + 2j, -3 + 0.5j, 0.25 - 4j, 7j).reshape(1, 4)
+    g = _c(2, 1j, -1).reshape(1, 3)
+    assert model.outputs(4, 0, 3, 1) == 6
+    y = model.synthesize(x, g, ONE, 1)
+    xp = np.concatenate([np.zeros(2, np.complex64), x[0], np.zeros(2, np.complex64)])
+    want = [2 * xp[n + 2] + 1j * xp[n + 1] - xp[n] for n in range(6)]
+    np.testing.assert_array_equal(y, np.array(want, np.complex64))
+
+
+def test_model_zero_stuffing_and_sample_and_hold():
+    x = _c(1 + 2j, -3, 5j).reshape(1, 3)
+    # T = 1, tap 1, rot 1, U = 3: x[0] 0 0 x[1] 0 0 x[2], then nothing more is reached
+    assert model.outputs(3, 0, 1, 3) == 7
+    y = model.synthesize(x, ONE, ONE, 3)
+    np.testing.assert_array_equal(y, _c(1 + 2j, 0, 0, -3, 0, 0, 5j))
+    # T = U all-ones taps: every sample held for U outputs
+    assert model.outputs(3, 0, 3, 3) == 9
+    y = model.synthesize(x, _c(1, 1, 1).reshape(1, 3), ONE, 3)
+    np.testing.assert_array_equal(y, np.repeat(x[0], 3))
+    # a larger count is legal: the tail is +0
+    y = model.synthesize(x, ONE, ONE, 3, n_out=12)
+    assert y.tobytes()[7 * 8:] == bytes(5 * 8)
+
+
+def test_model_a_phase_without_taps_is_plus_zero():
+    # T = 2 < U = 4: phases 2 and 3 have no taps, whatever the input (NaN and -0 included)
+    x = _c(np.nan, -0.0 - 0.0j, np.inf).reshape(1, 3)
+    y = model.synthesize(x, _c(1, 1).reshape(1, 2), ONE, 4, n_out=12)
+    for n in (2, 3, 6, 7, 10, 11):
+        assert y[n:n + 1].tobytes() == bytes(8)
+    assert np.isnan(y[0].real) and np.isnan(y[1].real)
+    # a phase with a tap, of a negative zero: the accumulators start at +0, so the sum is +0
+    assert y[4:5].tobytes() == bytes(8)
+
+
+def test_model_rot_first_wraps():
+    x = np.ones((1, 5), np.complex64)
+    rot = _c(1, 2, 3).reshape(1, 3)
+    np.testing.assert_array_equal(model.synthesize(x, ONE, rot, 1, rot_first=2), _c(3, 1, 2, 3, 1))
+    big = (1 << 40) + 3
+    np.testing.assert_array_equal(model.synthesize(x, ONE, rot, 1, rot_first=big),
+                                  _c(*[[1, 2, 3][(big + j) % 3] for j in range(5)]))
+    # the rotation belongs to the narrow sample, not to the output: U = 2 with a hold
+    np.testing.assert_array_equal(model.synthesize(x, _c(1, 1).reshape(1, 2), rot, 2, rot_first=1),
+                                  _c(2, 2, 3, 3, 1, 1, 2, 2, 3, 3))
+
+
+def test_model_two_blocks_equal_one_call():
+    rng = np.random.default_rng(5)
+    C, n_in, U, T, R = 2, 40, 3, 8, 5
+    x = (rng.standard_normal((C, n_in)) + 1j * rng.standard_normal((C, n_in))).astype(np.complex64)
+    g = (rng.standard_normal((C, T)) + 1j * rng.standard_normal((C, T))).astype(np.complex64)
+    rot = (rng.standard_normal((C, R)) + 1j * rng.standard_normal((C, R))).astype(np.complex64)
+    rf = (1 << 40) + 3
+    n_out = model.outputs(n_in, 0, T, U) + 4
+    one = model.synthesize(x, g, rot, U, 0, n_out, rf)
+    for w0 in (1, 50, 61, 100):
+        j0 = max(0, w0 // U - ((T + U - 1) // U - 1))      # the J0 that suffices
+        for J0 in {j0, j0 // 2}:
+            two = model.synthesize(x[:, J0:], g, rot, U, w0 - J0 * U, n_out - w0, rf + J0)
+            assert np.concatenate([one[:w0], two]).tobytes() == one.tobytes(), (w0, J0)
+        if j0 + 1 <= w0 // U and (T - 1 - w0 % U) // U == (T + U - 1) // U - 1:
+            # where output w0's chain has its full length, one sample later is one too few
+            late = model.synthesize(x[:, j0 + 1:], g, rot, U, w0 - (j0 + 1) * U, n_out - w0, rf + j0 + 1)
+            assert late.tobytes() != one[w0:].tobytes()
+
+
+def test_model_out_of_range_operands_are_plus_zero_and_products_are_formed():
+    # U = 1, T = 2, taps (1, nan): output 0 is x[0] * 1 + (+0) * nan = nan, by the definition
+    x = _c(1, 2, 3).reshape(1, 3)
+    y = model.synthesize(x, _c(1, np.nan).reshape(1, 2), ONE, 1)
+    assert np.isnan(y).all()
+    # an infinite tap against the missing sample behind the stream: 0 * inf = nan at the last output only
+    y = model.synthesize(x, _c(np.inf, 1).reshape(1, 2), ONE, 1)
+    assert np.isnan(y[3].real) and np.isinf(y[:3].real).all()
+    # the zero operand is +0, not a rotated zero: rot = nan must not reach it
+    y = model.synthesize(np.zeros((1, 0), np.complex64), _c(1, 1).reshape(1, 2), _c(np.nan).reshape(1, 1), 1, n_out=3)
+    assert y.tobytes() == bytes(24)
+    # the order of the sums over the chain, newest sample first (i grows as j falls):
+    # (1e8 - 1e8) + 1 = 1 in float32; the other way round, (1 - 1e8) + 1e8 = 0
+    y = model.synthesize(_c(1, -1e8, 1e8).reshape(1, 3), _c(1, 1, 1).reshape(1, 3), ONE, 1)
+    assert y[2] == 1
+    # and over the channels, channel 0 first
+    xs = _c(1e8, -1e8, 1).reshape(3, 1)
+    assert model.synthesize(xs, np.ones((3, 1), np.complex64), np.ones((3, 1), np.complex64), 1)[0] == 1
+
+
+@pytest.mark.parametrize("centres, interp, taps, cutoff, beta", [
+    ([F(-3, 10), F(1, 10), F(3, 10)], 8, 129, 0.09, 8.0),
+    ([F(0), F(1, 7), F(-5, 16), F(2, 5)], 16, 65, 1 / 40, 8.0),
+    ([F(1, 3)], 1, 1, 0.25, 5.0),
+    ([F(k, 8) - F(7, 16) for k in range(8)], 5, 64, 0.05, 6.5),
+])
+def test_design_helper_equals_the_model(centres, interp, taps, cutoff, beta):
+    import lphy
+    t, r, R, delay = lphy.synth_design(centres, interp, taps, cutoff, beta)
+    mt, mr, mR, mdelay = model.design(centres, interp, taps, cutoff, beta)
+    assert (R, delay) == (mR, mdelay) and t.dtype == r.dtype == np.complex64
+    assert t.shape == (len(centres), taps) and r.shape == (len(centres), R)
+    assert t.tobytes() == mt.tobytes() and r.tobytes() == mr.tobytes()
+    # what the tables mean: gain `interp` at the centre (unit gain for the
+    # zero-stuffed stream), R the period of the rotation
+    k = np.arange(taps)
+    for c, f in enumerate(centres):
+        gain = np.sum(t[c].astype(np.complex128) * np.exp(-2j * np.pi * float(f) * k))
+        assert abs(gain - interp) < 1e-5 * interp
+        assert abs(r[c, 1 % R] - np.exp(2j * np.pi * float(f * interp) * (1 % R))) < 1e-6
+
+
+def test_design_helper_refuses_a_long_period():
+    import lphy
+    assert lphy.synth_design([F(1, 65536)], 1, 3, 0.1, 8.0)[2] == 65536
+    with pytest.raises(ValueError):
+        lphy.synth_design([F(1, 65537)], 1, 3, 0.1, 8.0)
+    with pytest.raises(ValueError):
+        model.design([F(1, 65537)], 1, 3, 0.1, 8.0)
+    assert lphy.synth_design([F(1, 65537)], 65537, 3, 0.1, 8.0)[2] == 1
+
+
+@pytest.mark.parametrize("interp", [1, 8, 16, 5, 12])
+def test_design_tables_are_the_conjugates_of_the_channelisers(interp):
+    """Exactly: as values (a zero of either sign equal to a zero: the conjugate
+    of an imaginary part +0 is -0, where synth_design has +0), rot equals the
+    conjugate of chan_design's rot for decim = interp in every float32, for any
+    interp: both round the same float64 cosine and sine, and negating a float
+    is exact.  The taps equal U times the conjugate of chan_design's in every
+    float32 when U is a power of two: then h * U * cos in float64 is (h * cos)
+    * U exactly, and rounding to float32 commutes with a scaling by a power of
+    two (no value here is near the subnormal range: |taps| > 1e-30 or exactly
+    0).  For any other U the float64 products h * U * cos and (h * cos) * U may
+    round differently, so the float32 values agree to one unit in the last
+    place of float32, and that is what is asserted for them."""
+    import lphy
+    centres = [F(-3, 10), F(1, 10), F(3, 10), F(1, 7)]
+    T, cutoff, beta = 129, 0.4 / 8, 8.0
+    st, sr, sR, sd = lphy.synth_design(centres, interp, T, cutoff, beta)
+    ct, cr, cR, cd = lphy.chan_design(centres, interp, T, cutoff, beta)
+    assert (sR, sd) == (cR, cd)
+    assert not np.isnan(sr).any() and np.array_equal(sr, np.conj(cr))
+    want = np.conj(ct) * np.float32(interp)
+    nz = np.concatenate([np.abs(want.real[want.real != 0]), np.abs(want.imag[want.imag != 0])])
+    assert nz.min() > 1e-30
+    if interp & (interp - 1) == 0:
+        assert not np.isnan(st).any() and np.array_equal(st, want.astype(np.complex64))
+    else:
+        for a, b in ((st.real, want.real), (st.imag, want.imag)):
+            assert np.all(np.abs(a.astype(np.float64) - b.astype(np.float64)) <= np.spacing(np.abs(b)).astype(np.float64))
