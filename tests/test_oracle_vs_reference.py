@@ -413,3 +413,22 @@ def test_codes_whitening_across_periods(oracle, reference, kind):
                     assert not ((a ^ buf) & (0xFF ^ (0xFF >> (4 - rdd)))).any()
     buf = rng.integers(0, 256, 65535, dtype=np.uint8)
     np.testing.assert_array_equal(oracle.whiten(buf, kind, 9, 2), reference.whiten(buf, kind, 9, 2))
+
+
+# ---- lora_phy::decode on the decode case table (tests/decode_cases.py) -----
+# rows that do and do not carry a matching checksum, at the byte counts where
+# csrc/lphy_final.h branches; tests/test_gpu_decode.py leans on the oracle here
+import decode_cases as dc  # noqa: E402
+
+
+@pytest.mark.parametrize("nb", dc.NB_TABLE)
+def test_decode_case_table_bit_exact(oracle, reference, nb):
+    for variant in (0, 1, 2):
+        for kind in dc.kinds_for(nb):
+            syms = dc.row(oracle, nb, kind, variant)
+            a, b = oracle.decode(syms), reference.decode(syms)
+            assert a[0] == b[0] == nb, (kind, variant)
+            np.testing.assert_array_equal(a[1], b[1], err_msg=f"{kind} {variant}")
+            assert a[2] == b[2], (kind, variant)
+            want = dc.promised(nb, kind)
+            assert b[2] == (dc.CORRECTED_VERDICT[nb] if want is None else want), (kind, variant)
