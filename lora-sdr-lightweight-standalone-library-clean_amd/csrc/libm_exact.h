@@ -36,12 +36,10 @@
 #pragma once
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define LPHY_HD __host__ __device__ __forceinline__
-#else
+#include "lphy_hd.h"
+#if !defined(__HIPCC__)
 #include <math.h>
 #include <string.h>
-#define LPHY_HD static inline
 #endif
 
 namespace lphy_libm {

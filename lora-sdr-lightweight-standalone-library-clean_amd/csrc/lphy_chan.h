@@ -2,19 +2,19 @@
 // in, `channels` mixed, filtered and decimated streams out, by the definition
 // in include/lphy_hip.h: per (channel, output) one sequential chain of T
 // complex multiply-accumulates in separate float32 operations, then one
-// rotation.  The geometry and the argument check are lphy_chan_plan.h.  Only
+// rotation.  The geometry and the argument check are lphy_resample_plan.h.  Only
 // lphy_hip.hip includes it.
 //
 // One launch, one workgroup of kTile threads per tile of kChanTile consecutive
 // outputs of every channel; a lane owns one output m of the tile.
-//   LDS path (chan_lds_path: a full tile's padded span fits kChanLdsBytes):
+//   LDS path (chan_lds_path: a full tile's padded span fits kResLdsBytes):
 //     the workgroup stages the tile's span, (nout - 1) * D + T samples, once,
 //     with 16-byte loads between an 8-byte head and tail (`first` may be odd),
 //     into the padded image of chan_lds_slot.  Every sample then comes from
 //     HBM once per tile, whatever the number of channels.
 //   global path (every other plan: a long filter at a large D): the lanes read
 //     their samples from global memory.
-// Either way the channels go in groups of CG (chan_group: 1, 2, 4 or 8): per
+// Either way the channels go in groups of CG (res_group: 1, 2, 4 or 8): per
 // tap one 8-byte read of x and, per channel of the group, the tap g from a
 // wave-uniform address (a scalar load) and 8 VALU operations on the channel's
 // own accumulator pair, so a lane runs 2 * CG independent chains.  No chain is
@@ -22,7 +22,7 @@
 // no atomic, vector stores only.
 #pragma once
 #include "lphy_args.h"
-#include "lphy_chan_plan.h"
+#include "lphy_resample_plan.h"
 
 namespace {
 
@@ -102,18 +102,18 @@ void chan_launch_group(bool lds, dim3 grid, size_t lds_bytes, hipStream_t st, co
     else hipLaunchKernelGGL((k_chan<CG, false>), grid, dim3(kTile), 0, st, in, taps, rot, out, A);
 }
 
-inline void chan_launch(const lphy_chan_plan& p, const float* d_in, const float* d_taps, const float* d_rot,
-                        float* d_out, hipStream_t st) {
+inline void resample_launch(const lphy_chan_plan& p, const float* d_in, const float* d_taps, const float* d_rot,
+                            float* d_out, hipStream_t st) {
     const ChanArgs A{p.first, p.outputs, p.out_stride, p.channels, p.taps, p.decim, p.rot_period,
                      (unsigned)(p.rot_first % p.rot_period)};
     const bool lds = chan_lds_path(p.decim, p.taps);
     const size_t lds_bytes = lds ? (size_t)chan_lds_slots(p.decim, p.taps) * 8 : 0;
-    const dim3 grid((unsigned)chan_tiles(p.outputs));
+    const dim3 grid((unsigned)res_tiles(p.outputs));
     const float2* in = reinterpret_cast<const float2*>(d_in);
     const float2* taps = reinterpret_cast<const float2*>(d_taps);
     const float2* rot = reinterpret_cast<const float2*>(d_rot);
     float2* out = reinterpret_cast<float2*>(d_out);
-    switch (chan_group(p.channels)) {
+    switch (res_group(p.channels)) {
         case 1: chan_launch_group<1>(lds, grid, lds_bytes, st, in, taps, rot, out, A); break;
         case 2: chan_launch_group<2>(lds, grid, lds_bytes, st, in, taps, rot, out, A); break;
         case 4: chan_launch_group<4>(lds, grid, lds_bytes, st, in, taps, rot, out, A); break;

@@ -2,7 +2,7 @@
 // computes that is a function of plain values: the recurrences of the three
 // generators, their periods, and the reduction that takes (kind, bit_ofs, j)
 // to a table position or to a start state and a number of steps below one
-// period.  Plain C++ with LPHY_CP_HD in front of what the kernel calls too, no
+// period.  Plain C++ with LPHY_HD in front of what the kernel calls too, no
 // HIP: the kernel, the entry point and a CPU test
 // (tests/cpp/codes_plan_check.cpp, which derives the periods again by
 // stepping the recurrences until the state returns) share it.
@@ -10,12 +10,7 @@
 #include <cstdint>
 
 #include "../../include/lphy_hip.h"
-
-#if defined(__HIPCC__)
-#define LPHY_CP_HD __host__ __device__ __forceinline__
-#else
-#define LPHY_CP_HD inline
-#endif
+#include "lphy_hd.h"
 
 // The stored 510-bit sequence of Sx1272ComputeWhitening and the sequence
 // positions its codeword bits tap (LoRaCodes.hpp:147-167), as initialisers:
@@ -37,22 +32,22 @@ constexpr int kWhitenTapMin = -360;            // the most negative tap: tap + k
 constexpr unsigned kWhitenSx1232Seed = 0x1FF;
 
 // SX1232RadioComputeWhitening (LoRaCodes.hpp:111-137): x^9 + x^5 + 1, one bit
-LPHY_CP_HD unsigned whiten_sx1232_step(unsigned s) { return (s >> 1) | (((s ^ (s >> 5)) & 1u) << 8); }
+LPHY_HD unsigned whiten_sx1232_step(unsigned s) { return (s >> 1) | (((s ^ (s >> 5)) & 1u) << 8); }
 
 // Sx1272ComputeWhiteningLfsr (:176-189): one codeword, poly 0x1D on every bit lane
-LPHY_CP_HD unsigned long long whiten_lfsr64_step(unsigned long long r) {
+LPHY_HD unsigned long long whiten_lfsr64_step(unsigned long long r) {
     return (r >> 8) | (((r >> 32) ^ (r >> 24) ^ (r >> 16) ^ r) << 56);
 }
 
 // the state that even (odd = 0) and odd codeword positions start from
-LPHY_CP_HD unsigned long long whiten_lfsr_seed(unsigned rdd, unsigned odd) {
+LPHY_HD unsigned long long whiten_lfsr_seed(unsigned rdd, unsigned odd) {
     return rdd == 1 ? (odd ? 0xF8ECFEEFEFEFEFEFull : 0x05121100F8ECFEEFull)
                     : (odd ? 0xE85C2EFFFFFFFFFFull : 0x6572D100E85C2EFFull);
 }
 
 // What the entry point hands the kernel for a bit_ofs >= 0: the two SX1272
 // kinds repeat every kWhitenSeqLen positions, SX1232 ignores it.
-LPHY_CP_HD unsigned whiten_reduce_ofs(int kind, int bit_ofs) {
+LPHY_HD unsigned whiten_reduce_ofs(int kind, int bit_ofs) {
     return kind == LPHY_WHITEN_SX1232 ? 0u : (unsigned)bit_ofs % kWhitenSeqLen;
 }
 
@@ -60,10 +55,10 @@ LPHY_CP_HD unsigned whiten_reduce_ofs(int kind, int bit_ofs) {
 // byte's index in its row, so ofs + j and 8 * j are far from 32 bits.
 
 // SX1232: steps from kWhitenSx1232Seed to the state whose low byte masks byte j
-LPHY_CP_HD unsigned whiten_sx1232_steps(unsigned j) { return (8u * j) % kWhitenSx1232Period; }
+LPHY_HD unsigned whiten_sx1232_steps(unsigned j) { return (8u * j) % kWhitenSx1232Period; }
 
 // SX1272: position in the stored sequence of a codeword bit with tap `tap`
-LPHY_CP_HD unsigned whiten_seq_pos(int tap, unsigned ofs, unsigned j) {
+LPHY_HD unsigned whiten_seq_pos(int tap, unsigned ofs, unsigned j) {
     return ((unsigned)(tap + (int)kWhitenSeqLen) + ofs + j) % kWhitenSeqLen;
 }
 
@@ -72,7 +67,7 @@ LPHY_CP_HD unsigned whiten_seq_pos(int tap, unsigned ofs, unsigned j) {
 struct WhitenLfsrPlan {
     unsigned odd, steps;
 };
-LPHY_CP_HD WhitenLfsrPlan whiten_lfsr_plan(unsigned ofs, unsigned j) {
+LPHY_HD WhitenLfsrPlan whiten_lfsr_plan(unsigned ofs, unsigned j) {
     const unsigned p = ofs + j;
     return WhitenLfsrPlan{p & 1u, (p >> 1) % kWhitenLfsrPeriod};
 }
@@ -80,7 +75,7 @@ LPHY_CP_HD WhitenLfsrPlan whiten_lfsr_plan(unsigned ofs, unsigned j) {
 // The byte XORed into byte j of a row.  seq: the 8 words of
 // LPHY_WHITEN_SEQ_INIT; taps: LPHY_WHITEN_TAPS_CR1_INIT for rdd 1,
 // LPHY_WHITEN_TAPS_INIT otherwise (both read by LPHY_WHITEN_SX1272 only).
-LPHY_CP_HD unsigned whiten_mask(int kind, unsigned ofs, unsigned j, unsigned rdd, const unsigned long long* seq,
+LPHY_HD unsigned whiten_mask(int kind, unsigned ofs, unsigned j, unsigned rdd, const unsigned long long* seq,
                                 const int* taps) {
     if (kind == LPHY_WHITEN_SX1232) {
         unsigned s = kWhitenSx1232Seed;

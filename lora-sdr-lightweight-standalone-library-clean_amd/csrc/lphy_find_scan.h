@@ -9,12 +9,7 @@
 #include <cstdint>
 
 #include "lphy_ragged_layout.h"
-
-#if defined(__HIPCC__)
-#define LPHY_FF_HD __host__ __device__ __forceinline__
-#else
-#define LPHY_FF_HD inline
-#endif
+#include "lphy_hd.h"
 
 namespace lphy {
 
@@ -34,12 +29,12 @@ struct FindSum {
 constexpr FindSum kFindEmpty = {kFindNone, kFindNone, kFindNone};
 
 // one window
-LPHY_FF_HD FindSum find_leaf(uint32_t w, bool active) { return active ? FindSum{w, w, w} : kFindEmpty; }
+LPHY_HD FindSum find_leaf(uint32_t w, bool active) { return active ? FindSum{w, w, w} : kFindEmpty; }
 
 // Segment A followed by segment B.  The gap between A's last and B's first
 // active window decides whether B's first window really starts a burst; if it
 // does not and B has no later start, the last start is A's.  Associative.
-LPHY_FF_HD FindSum find_join(const FindSum& a, const FindSum& b, uint32_t max_gap) {
+LPHY_HD FindSum find_join(const FindSum& a, const FindSum& b, uint32_t max_gap) {
     if (a.first == kFindNone) return b;
     if (b.first == kFindNone) return a;
     const bool bridged = b.first - a.last - 1 <= max_gap;
@@ -65,7 +60,7 @@ struct FindBurst {
 // The burst of windows a .. b (lphy_hip.h, "Frame search", 3 and 4).  No sum
 // wraps for arguments that passed find_frames_args: first + lead + windows *
 // hop <= 2^48 and windows * hop / step < 2^32.
-LPHY_FF_HD FindBurst find_burst(const FindGeo& g, uint32_t a, uint32_t b) {
+LPHY_HD FindBurst find_burst(const FindGeo& g, uint32_t a, uint32_t b) {
     FindBurst r;
     r.start = g.first + g.lead + (uint64_t)a * g.hop;
     uint64_t extent = 0;

@@ -721,60 +721,54 @@ int lphy_hip_find_frames(lphy_hip_ctx* c, const lphy_detect_rec* d_rec, size_t w
     return find_frames_impl(c, d_rec, windows, *p, mode, max_frames, d_desc, d_info, d_work, (hipStream_t)stream);
 }
 
-// ---- the channeliser (lphy_chan.h) -------------------------------------------
+// ---- the channeliser (lphy_chan.h) and the synthesiser (lphy_synth.h) ---------
 uint64_t lphy_hip_channelize_outputs(uint64_t in_samples, uint64_t first, uint32_t taps, uint32_t decim) {
     return chan_outputs(in_samples, first, taps, decim);
 }
-
-namespace {
-int channelize_check(const lphy_hip_ctx* c, const float* in, const lphy_chan_plan* p, const float* taps,
-                     const float* rot, const float* out) {
-    return chan_args(c != nullptr, p, taps && rot, in != nullptr, out != nullptr, chan_aligned(in, taps, rot, out));
-}
-
-// The one launch; the plan has passed channelize_check and has outputs > 0.
-int channelize_impl(lphy_hip_ctx* c, const float* d_in, const lphy_chan_plan& p, const float* d_taps,
-                    const float* d_rot, float* d_out, hipStream_t st) {
-    HIP_OK(hipSetDevice(c->device));
-    chan_launch(p, d_in, d_taps, d_rot, d_out, st);
-    HIP_OK(hipGetLastError());
-    return 0;
-}
-}  // namespace
-
-int lphy_hip_channelize(lphy_hip_ctx* c, const float* d_in, const lphy_chan_plan* p, const float* d_taps,
-                        const float* d_rot, float* d_out, void* stream) {
-    if (int rc = channelize_check(c, d_in, p, d_taps, d_rot, d_out)) return rc;
-    if (p->outputs == 0) return 0;
-    return channelize_impl(c, d_in, *p, d_taps, d_rot, d_out, (hipStream_t)stream);
-}
-
-// ---- the synthesiser (lphy_synth.h) ------------------------------------------
 uint64_t lphy_hip_synthesize_outputs(uint64_t in_samples, uint64_t first, uint32_t taps, uint32_t interp) {
     return synth_outputs(in_samples, first, taps, interp);
 }
 
+extern "C++" {
 namespace {
-int synthesize_check(const lphy_hip_ctx* c, const float* in, const lphy_synth_plan* p, const float* taps,
-                     const float* rot, const float* out) {
-    return synth_args(c != nullptr, p, taps && rot, in != nullptr, out != nullptr, synth_aligned(in, taps, rot, out));
+// Both calls' argument check; a plan that passes with outputs == 0 is done
+// (1, for the caller to return 0), as the *_host forms need to know too.
+// `args`: chan_args or synth_args.
+template <class Plan>
+int resample_check(int (*args)(bool, const Plan*, bool, bool, bool, bool), const lphy_hip_ctx* c, const float* in,
+                   const Plan* p, const float* taps, const float* rot, const float* out) {
+    if (int rc = args(c != nullptr, p, taps && rot, in != nullptr, out != nullptr, res_aligned(in, taps, rot, out)))
+        return rc;
+    return p->outputs == 0;
 }
 
-// The one launch; the plan has passed synthesize_check and has outputs > 0.
-int synthesize_impl(lphy_hip_ctx* c, const float* d_in, const lphy_synth_plan& p, const float* d_taps,
-                    const float* d_rot, float* d_out, hipStream_t st) {
+// The one launch (resample_launch of lphy_chan.h or lphy_synth.h, by the plan's
+// type); the plan has passed resample_check and has outputs > 0.
+template <class Plan>
+int resample_impl(lphy_hip_ctx* c, const float* d_in, const Plan& p, const float* d_taps, const float* d_rot,
+                  float* d_out, hipStream_t st) {
     HIP_OK(hipSetDevice(c->device));
-    synth_launch(p, d_in, d_taps, d_rot, d_out, st);
+    resample_launch(p, d_in, d_taps, d_rot, d_out, st);
     HIP_OK(hipGetLastError());
     return 0;
 }
-}  // namespace
 
+template <class Plan>
+int resample_entry(int (*args)(bool, const Plan*, bool, bool, bool, bool), lphy_hip_ctx* c, const float* d_in,
+                   const Plan* p, const float* d_taps, const float* d_rot, float* d_out, void* stream) {
+    if (int rc = resample_check(args, c, d_in, p, d_taps, d_rot, d_out)) return rc > 0 ? 0 : rc;
+    return resample_impl(c, d_in, *p, d_taps, d_rot, d_out, (hipStream_t)stream);
+}
+}  // namespace
+}  // extern "C++"
+
+int lphy_hip_channelize(lphy_hip_ctx* c, const float* d_in, const lphy_chan_plan* p, const float* d_taps,
+                        const float* d_rot, float* d_out, void* stream) {
+    return resample_entry(chan_args, c, d_in, p, d_taps, d_rot, d_out, stream);
+}
 int lphy_hip_synthesize(lphy_hip_ctx* c, const float* d_in, const lphy_synth_plan* p, const float* d_taps,
                         const float* d_rot, float* d_out, void* stream) {
-    if (int rc = synthesize_check(c, d_in, p, d_taps, d_rot, d_out)) return rc;
-    if (p->outputs == 0) return 0;
-    return synthesize_impl(c, d_in, *p, d_taps, d_rot, d_out, (hipStream_t)stream);
+    return resample_entry(synth_args, c, d_in, p, d_taps, d_rot, d_out, stream);
 }
 
 int lphy_hip_detect_serial_count(lphy_hip_ctx* c, unsigned long long* out, int reset) {

@@ -208,8 +208,7 @@ int lphy_hip_find_frames_host(lphy_hip_ctx* c, const lphy_detect_rec* h_rec, siz
 // owns come back as they went.
 int lphy_hip_channelize_host(lphy_hip_ctx* c, const float* h_in, const lphy_chan_plan* p, const float* h_taps,
                              const float* h_rot, float* h_out) {
-    if (int rc = channelize_check(c, h_in, p, h_taps, h_rot, h_out)) return rc;
-    if (p->outputs == 0) return 0;
+    if (int rc = resample_check(chan_args, c, h_in, p, h_taps, h_rot, h_out)) return rc > 0 ? 0 : rc;
     lphy_chan_plan q = *p;
     q.in_samples = (p->outputs - 1) * p->decim + p->taps;
     q.first = 0;
@@ -217,8 +216,8 @@ int lphy_hip_channelize_host(lphy_hip_ctx* c, const float* h_in, const lphy_chan
     if (int rc = hc.begin(chan_plan(q.in_samples, p->channels, p->taps, p->rot_period, p->out_stride),
                           {h_in + 2 * p->first, h_taps, h_rot, h_out}))
         return rc;
-    return hc.finish(channelize_impl(c, hc.dev<float>(0), q, hc.dev<float>(1), hc.dev<float>(2), hc.dev<float>(3),
-                                     hc.stream()));
+    return hc.finish(
+        resample_impl(c, hc.dev<float>(0), q, hc.dev<float>(1), hc.dev<float>(2), hc.dev<float>(3), hc.stream()));
 }
 
 // The synthesiser on host buffers: the channels' streams (from the first
@@ -226,15 +225,14 @@ int lphy_hip_channelize_host(lphy_hip_ctx* c, const float* h_in, const lphy_chan
 // two tables in, the one launch, `outputs` samples back.
 int lphy_hip_synthesize_host(lphy_hip_ctx* c, const float* h_in, const lphy_synth_plan* p, const float* h_taps,
                              const float* h_rot, float* h_out) {
-    if (int rc = synthesize_check(c, h_in, p, h_taps, h_rot, h_out)) return rc;
-    if (p->outputs == 0) return 0;
+    if (int rc = resample_check(synth_args, c, h_in, p, h_taps, h_rot, h_out)) return rc > 0 ? 0 : rc;
     const size_t in = p->in_samples ? (size_t)((p->channels - 1) * p->in_stride + p->in_samples) : 0;
     HostCall hc(c, kPageable);
     if (int rc = hc.begin(synth_plan(in, p->channels, p->taps, p->rot_period, p->outputs),
                           {h_in, h_taps, h_rot, h_out}))
         return rc;
-    return hc.finish(synthesize_impl(c, hc.dev<float>(0), *p, hc.dev<float>(1), hc.dev<float>(2), hc.dev<float>(3),
-                                     hc.stream()));
+    return hc.finish(
+        resample_impl(c, hc.dev<float>(0), *p, hc.dev<float>(1), hc.dev<float>(2), hc.dev<float>(3), hc.stream()));
 }
 
 int lphy_hip_decode_host(lphy_hip_ctx* c, const uint16_t* h_syms, size_t count,

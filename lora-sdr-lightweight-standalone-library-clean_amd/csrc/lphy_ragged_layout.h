@@ -15,6 +15,7 @@
 
 #include "../../include/lphy_hip.h"
 
+// not lphy_hd.h's LPHY_HD: this one stands before `constexpr` and `inline`, here and in lphy_lorawan_ragged.h
 #if defined(__HIPCC__)
 #define LPHY_RG_HD __host__ __device__
 #else

@@ -7,19 +7,14 @@
 #include <cstdint>
 
 #include "../../include/lphy_hip.h"
-
-#if defined(__HIPCC__)
-#define LPHY_RU_HD __host__ __device__ __forceinline__
-#else
-#define LPHY_RU_HD inline
-#endif
+#include "lphy_hd.h"
 
 namespace lphy {
 
 // Frame of unit u in a ragged table (lphy_ragged_desc, frames + 1 records):
 // the last record whose unit_offset is <= u, for u below the table's total
 // (whatever the table holds, a frame below nframes).
-LPHY_RU_HD unsigned unit_frame(const lphy_ragged_desc* __restrict__ desc, unsigned nframes, unsigned long long u) {
+LPHY_HD unsigned unit_frame(const lphy_ragged_desc* __restrict__ desc, unsigned nframes, unsigned long long u) {
     // unit_offset[lo] <= u < unit_offset[hi] throughout
     unsigned lo = 0, hi = nframes;
     while (hi - lo > 1) {
@@ -43,7 +38,7 @@ struct RaggedUnit {
 // own offset, so a table whose prefix is wrong cannot lead outside the frame
 // once the caller has checked s against the frame's own count.
 template <bool UNIFORM>
-LPHY_RU_HD RaggedUnit ragged_unit(const lphy_ragged_desc* __restrict__ desc, unsigned nframes,
+LPHY_HD RaggedUnit ragged_unit(const lphy_ragged_desc* __restrict__ desc, unsigned nframes,
                                   unsigned long long units, unsigned long long u) {
 #if defined(__HIP_DEVICE_COMPILE__)
     if constexpr (UNIFORM) {

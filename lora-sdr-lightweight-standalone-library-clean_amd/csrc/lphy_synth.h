@@ -3,14 +3,14 @@
 // definition in include/lphy_hip.h: per (output, channel) one sequential chain
 // of up to ceil(T / U) complex multiply-accumulates in separate float32
 // operations over rotated narrow samples, the channels' sums added in channel
-// order.  The geometry and the argument check are lphy_synth_plan.h.  Only
+// order.  The geometry and the argument check are lphy_resample_plan.h.  Only
 // lphy_hip.hip includes it.
 //
 // One launch, one workgroup of kTile threads per tile of kSynthTile consecutive
 // outputs; a lane owns one output w = first + n, its q = w / U and p = w % U.
-// The channels go in groups of CG (synth_group: 1, 2, 4 or 8), so a lane runs
+// The channels go in groups of CG (res_group: 1, 2, 4 or 8), so a lane runs
 // 2 * CG independent chains; no chain is split.
-//   LDS path (synth_lds_path: one group's image fits kSynthLdsBytes): per group
+//   LDS path (synth_lds_path: one group's image fits kResLdsBytes): per group
 //     the workgroup stages the span of synth_tile_span, already rotated and
 //     with (+0, +0) where j is outside the stream, so the rotation (and its
 //     index modulo R) costs per input sample, not per tap.  A lane then reads x
@@ -22,7 +22,7 @@
 // No workgroup waits on another, no atomic, vector stores only.
 #pragma once
 #include "lphy_args.h"
-#include "lphy_synth_plan.h"
+#include "lphy_resample_plan.h"
 
 namespace {
 
@@ -138,18 +138,18 @@ void synth_launch_group(bool lds, dim3 grid, size_t lds_bytes, hipStream_t st, c
     else hipLaunchKernelGGL((k_synth<CG, false>), grid, dim3(kTile), 0, st, in, taps, rot, out, A);
 }
 
-inline void synth_launch(const lphy_synth_plan& p, const float* d_in, const float* d_taps, const float* d_rot,
-                         float* d_out, hipStream_t st) {
+inline void resample_launch(const lphy_synth_plan& p, const float* d_in, const float* d_taps, const float* d_rot,
+                            float* d_out, hipStream_t st) {
     const SynthArgs A{p.first,  p.outputs, p.in_samples, p.in_stride, p.channels,
                       p.taps,   p.interp,  p.rot_period, (unsigned)(p.rot_first % p.rot_period)};
     const bool lds = synth_lds_path(p.channels, p.interp, p.taps);
     const size_t lds_bytes = lds ? (size_t)synth_lds_bytes(p.channels, p.interp, p.taps) : 0;
-    const dim3 grid((unsigned)synth_tiles(p.outputs));
+    const dim3 grid((unsigned)res_tiles(p.outputs));
     const float2* in = reinterpret_cast<const float2*>(d_in);
     const float2* taps = reinterpret_cast<const float2*>(d_taps);
     const float2* rot = reinterpret_cast<const float2*>(d_rot);
     float2* out = reinterpret_cast<float2*>(d_out);
-    switch (synth_group(p.channels)) {
+    switch (res_group(p.channels)) {
         // one channel's image always fits (synth_lds_path; 34,824 bytes at most): no k_synth<1, false>
         case 1: hipLaunchKernelGGL((k_synth<1, true>), grid, dim3(kTile), lds_bytes, st, in, taps, rot, out, A); break;
         case 2: synth_launch_group<2>(lds, grid, lds_bytes, st, in, taps, rot, out, A); break;

@@ -116,7 +116,7 @@ CHAN_PLAN = np.dtype([("first", "<u8"), ("in_samples", "<u8"), ("outputs", "<u8"
                       ("rot_first", "<u8"), ("channels", "<u4"), ("taps", "<u4"), ("decim", "<u4"),
                       ("rot_period", "<u4"), ("reserved", "<u4", (2,))])
 assert CHAN_PLAN.itemsize == 64
-CHAN_TILE = 256  # outputs of every channel per workgroup (csrc/lphy_chan_plan.h kChanTile)
+CHAN_TILE = 256  # outputs of every channel per workgroup (csrc/lphy_resample_plan.h kResTile)
 
 
 def chan_plan(first=0, in_samples=0, outputs=0, out_stride=0, rot_first=0, channels=0, taps=0, decim=0,
@@ -185,7 +185,7 @@ SYNTH_PLAN = np.dtype([("first", "<u8"), ("in_samples", "<u8"), ("in_stride", "<
                        ("rot_first", "<u8"), ("channels", "<u4"), ("taps", "<u4"), ("interp", "<u4"),
                        ("rot_period", "<u4"), ("reserved", "<u4", (2,))])
 assert SYNTH_PLAN.itemsize == 64
-SYNTH_TILE = 256  # wideband outputs per workgroup (csrc/lphy_synth_plan.h kSynthTile)
+SYNTH_TILE = 256  # wideband outputs per workgroup (csrc/lphy_resample_plan.h kResTile)
 
 
 def synth_plan(first=0, in_samples=0, in_stride=0, outputs=0, rot_first=0, channels=0, taps=0, interp=0,
@@ -402,6 +402,27 @@ def _dev_buf(t, name: str, device: int, nbytes: int, itemsize: int | None = None
     if have < nbytes:
         raise ValueError(f"{name}: {have} bytes, the call writes/reads {nbytes}")
     return t.data_ptr()
+
+
+# what channelize / synthesize and their *_host forms share
+def _one_plan(plan, dtype, name: str):
+    p = np.ascontiguousarray(plan, dtype).reshape(-1)
+    if p.size != 1:
+        raise ValueError(f"plan: one {name} record expected, got {p.size}")
+    return p, p[0]
+
+
+def _tables_bufs(taps, rot, device: int, q):
+    ch = int(q["channels"])
+    return (_dev_buf(taps, "taps", device, ch * int(q["taps"]) * 8, None),
+            _dev_buf(rot, "rot", device, ch * int(q["rot_period"]) * 8, None))
+
+
+_PAD = np.zeros(1, np.complex64)  # an empty array's stand-in: never read, never written
+
+
+def _host_ptrs(*arrays):
+    return [(a if a.size else _PAD).ctypes.data for a in arrays]
 
 
 class Demodulator:
@@ -652,15 +673,10 @@ class Demodulator:
         channels x out_stride complex samples, of which the call writes the
         first `outputs` of every channel.  Asynchronous."""
         dv = self.device
-        p = np.ascontiguousarray(plan, CHAN_PLAN).reshape(-1)
-        if p.size != 1:
-            raise ValueError(f"plan: one CHAN_PLAN record expected, got {p.size}")
-        q = p[0]
-        ch = int(q["channels"])
+        p, q = _one_plan(plan, CHAN_PLAN, "CHAN_PLAN")
         p_in = _dev_buf(iq, "iq", dv, int(q["in_samples"]) * 8, None)
-        p_taps = _dev_buf(taps, "taps", dv, ch * int(q["taps"]) * 8, None)
-        p_rot = _dev_buf(rot, "rot", dv, ch * int(q["rot_period"]) * 8, None)
-        p_out = _dev_buf(out, "out", dv, ch * int(q["out_stride"]) * 8, None)
+        p_taps, p_rot = _tables_bufs(taps, rot, dv, q)
+        p_out = _dev_buf(out, "out", dv, int(q["channels"]) * int(q["out_stride"]) * 8, None)
         _chk(self.lib.lphy_hip_channelize(self.ctx, p_in, p.ctypes.data, p_taps, p_rot, p_out, stream),
              "lphy_hip_channelize")
 
@@ -685,10 +701,8 @@ class Demodulator:
                 or out.shape[1] < outputs):
             raise ValueError(f"out: C-contiguous complex64 [{t.shape[0]}, >= {outputs}] expected")
         p = chan_plan(first, x.size, outputs, out.shape[1], rot_first, t.shape[0], t.shape[1], decim, r.shape[1])
-        pad = np.zeros(1, np.complex64)
-        _chk(self.lib.lphy_hip_channelize_host(self.ctx, (x if x.size else pad).ctypes.data, p.ctypes.data,
-                                               (t if t.size else pad).ctypes.data, (r if r.size else pad).ctypes.data,
-                                               (out if out.size else pad).ctypes.data),
+        p_x, p_t, p_r, p_out = _host_ptrs(x, t, r, out)
+        _chk(self.lib.lphy_hip_channelize_host(self.ctx, p_x, p.ctypes.data, p_t, p_r, p_out),
              "lphy_hip_channelize_host")
         return out[:, :outputs]
 
@@ -705,17 +719,13 @@ class Demodulator:
         samples (synth_design()); `out`: device tensor of `outputs` complex
         samples.  Asynchronous."""
         dv = self.device
-        p = np.ascontiguousarray(plan, SYNTH_PLAN).reshape(-1)
-        if p.size != 1:
-            raise ValueError(f"plan: one SYNTH_PLAN record expected, got {p.size}")
-        q = p[0]
+        p, q = _one_plan(plan, SYNTH_PLAN, "SYNTH_PLAN")
         ch, n_in = int(q["channels"]), int(q["in_samples"])
         p_in = None
         if streams is not None or n_in:
             p_in = _dev_buf(streams, "streams", dv, ((max(ch, 1) - 1) * int(q["in_stride"]) + n_in) * 8 if n_in else 0,
                             None)
-        p_taps = _dev_buf(taps, "taps", dv, ch * int(q["taps"]) * 8, None)
-        p_rot = _dev_buf(rot, "rot", dv, ch * int(q["rot_period"]) * 8, None)
+        p_taps, p_rot = _tables_bufs(taps, rot, dv, q)
         p_out = _dev_buf(out, "out", dv, int(q["outputs"]) * 8, None)
         _chk(self.lib.lphy_hip_synthesize(self.ctx, p_in, p.ctypes.data, p_taps, p_rot, p_out, stream),
              "lphy_hip_synthesize")
@@ -736,10 +746,8 @@ class Demodulator:
             outputs = synthesize_outputs(x.shape[1], first, t.shape[1], interp)
         out = np.zeros(outputs, np.complex64)
         p = synth_plan(first, x.shape[1], x.shape[1], outputs, rot_first, t.shape[0], t.shape[1], interp, r.shape[1])
-        pad = np.zeros(1, np.complex64)
-        _chk(self.lib.lphy_hip_synthesize_host(self.ctx, (x if x.size else pad).ctypes.data, p.ctypes.data,
-                                               (t if t.size else pad).ctypes.data, (r if r.size else pad).ctypes.data,
-                                               (out if out.size else pad).ctypes.data),
+        p_x, p_t, p_r, p_out = _host_ptrs(x, t, r, out)
+        _chk(self.lib.lphy_hip_synthesize_host(self.ctx, p_x, p.ctypes.data, p_t, p_r, p_out),
              "lphy_hip_synthesize_host")
         return out
 

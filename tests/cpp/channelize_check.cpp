@@ -1,5 +1,5 @@
 // Stand-alone program over the host-compilable part of the channeliser
-// (csrc/lphy_chan_plan.h), for a run under the host sanitizers
+// (csrc/lphy_resample_plan.h), for a run under the host sanitizers
 // (tests/test_channelize_cpu.py):
 //   - every row of chan_args in the documented order, pairs of bad arguments
 //     (the earlier row wins), and the overflow-prone rows with values near
@@ -10,12 +10,13 @@
 //   - the LDS image: chan_lds_slot is strictly increasing and stays inside
 //     chan_lds_slots, the lanes of a half-wave fall on at least 31 slot columns
 //     at the decimations the padding is for, and chan_lds_path is the size rule;
-//   - chan_group.
+//   - res_group.
 #include <cstdio>
 #include <initializer_list>
 #include <vector>
 
-#include "lphy_chan_plan.h"
+#include "lphy_resample_plan.h"
+#include "resample_pairs.h"
 
 using namespace lphy;
 
@@ -74,11 +75,11 @@ static int args_check() {
     EXPECT(args(p) == 0);
     p.channels = 65;
     EXPECT(args(p) == -ERANGE);
-    // chan_aligned: any of the four off an 8-byte boundary, null pointers pass
+    // res_aligned: any of the four off an 8-byte boundary, null pointers pass
     alignas(16) static char buf[32];
-    EXPECT(chan_aligned(buf, buf + 8, buf + 16, nullptr));
-    EXPECT(!chan_aligned(buf + 4, buf, buf, buf) && !chan_aligned(buf, buf + 4, buf, buf));
-    EXPECT(!chan_aligned(buf, buf, buf + 2, buf) && !chan_aligned(buf, buf, buf, buf + 1));
+    EXPECT(res_aligned(buf, buf + 8, buf + 16, nullptr));
+    EXPECT(!res_aligned(buf + 4, buf, buf, buf) && !res_aligned(buf, buf + 4, buf, buf));
+    EXPECT(!res_aligned(buf, buf, buf + 2, buf) && !res_aligned(buf, buf, buf, buf + 1));
 
     // the -ERANGE rows, each at its edge
     p = good(), p.channels = 64, p.out_stride = p.outputs;
@@ -200,7 +201,7 @@ static int geometry_check() {
         for (uint32_t D : {1u, 3u, 4u, 7u, 16u, 65536u})
             for (uint32_t T : {1u, 2u, 5u, 67u, 4096u})
                 for (uint64_t outputs : {uint64_t(1), K - 1, K, K + 1, 3 * K + 5}) {
-                    const uint64_t tiles = chan_tiles(outputs);
+                    const uint64_t tiles = res_tiles(outputs);
                     EXPECT(tiles == (outputs + K - 1) / K);
                     uint64_t seen = 0;
                     for (uint64_t t = 0; t < tiles; ++t) {
@@ -241,15 +242,15 @@ static int lds_check() {
                 for (uint32_t l = l0; l < l0 + 32; ++l) used += col[chan_lds_slot(l * D + k) & 31]++ == 0;
                 EXPECT(used >= 31 && (k >= D || used == 32));  // unpadded: 32 / D of them
             }
-    // the size rule at its edge: slots * 8 <= kChanLdsBytes
+    // the size rule at its edge: slots * 8 <= kResLdsBytes
     EXPECT(chan_lds_path(16, 129) && chan_lds_path(8, 65) && chan_lds_path(1, 4096) && chan_lds_path(8, 4096));
     EXPECT(!chan_lds_path(64, 4096) && !chan_lds_path(65536, 1));
     for (uint32_t D = 1; D <= 64; ++D)
         for (uint32_t T : {1u, 64u, 4096u})
-            EXPECT(chan_lds_path(D, T) == (chan_lds_slots(D, T) * 8 <= kChanLdsBytes));
+            EXPECT(chan_lds_path(D, T) == (chan_lds_slots(D, T) * 8 <= kResLdsBytes));
     uint32_t Tedge = 1;
     while (chan_lds_path(24, Tedge + 1)) ++Tedge;
-    EXPECT(chan_lds_slots(24, Tedge) * 8 <= kChanLdsBytes && chan_lds_slots(24, Tedge + 1) * 8 > kChanLdsBytes);
+    EXPECT(chan_lds_slots(24, Tedge) * 8 <= kResLdsBytes && chan_lds_slots(24, Tedge + 1) * 8 > kResLdsBytes);
     // no wrap at the largest plan
     EXPECT(chan_lds_slots(65536, 4096) > (uint64_t(1) << 24));
     return 0;
@@ -257,14 +258,28 @@ static int lds_check() {
 
 static int group_check() {
     const unsigned want[] = {0, 1, 2, 4, 4, 8, 8, 8, 8, 8};
-    for (unsigned c = 1; c < 10; ++c) EXPECT(chan_group(c) == want[c]);
-    EXPECT(chan_group(64) == 8);
+    for (unsigned c = 1; c < 10; ++c) EXPECT(res_group(c) == want[c]);
+    EXPECT(res_group(64) == 8);
     return 0;
 }
 
+// two violations at once, one row per adjacent pair of chan_args's tests and some across the two codes
+static const Pair kChanPairs[] = {
+    {V_CTX, V_PLAN, -EINVAL}, {V_PLAN, V_TABLES, -EINVAL}, {V_TABLES, V_IN, -EINVAL}, {V_IN, V_OUT, -EINVAL},
+    {V_OUT, V_ALIGN, -EINVAL}, {V_ALIGN, V_RES0, -EINVAL}, {V_RES0, V_RES1, -EINVAL}, {V_RES1, V_CH0, -EINVAL},
+    {V_CH0, V_T0, -EINVAL}, {V_T0, V_STEP0, -EINVAL}, {V_STEP0, V_R0, -EINVAL}, {V_R0, V_CHMAX, -EINVAL},
+    {V_CHMAX, V_TMAX, -ERANGE}, {V_TMAX, V_STEPMAX, -ERANGE}, {V_STEPMAX, V_RMAX, -ERANGE},
+    {V_RMAX, V_OUTMAX, -ERANGE}, {V_OUTMAX, V_STRIDE_SMALL, -ERANGE}, {V_STRIDE_SMALL, V_INMAX, -ERANGE},
+    {V_INMAX, V_FIRST, -ERANGE}, {V_FIRST, V_STRIDE_BIG, -ERANGE}, {V_CHMAX, V_RES0, -EINVAL},
+    {V_INMAX, V_STRIDE_SMALL, -ERANGE}, {V_CHMAX, V_ALIGN, -EINVAL}, {V_OUTMAX, V_RES1, -EINVAL},
+    {V_STRIDE_BIG, V_R0, -EINVAL}, {V_INMAX, V_OUT, -EINVAL}, {V_FIRST, V_CTX, -EINVAL}, {V_STEPMAX, V_T0, -EINVAL},
+    {V_STRIDE_BIG, V_TABLES, -EINVAL}, {V_RMAX, V_IN, -EINVAL}, {V_FIRST, V_STEP0, -EINVAL}, {V_TMAX, V_CH0, -EINVAL},
+    {V_STRIDE_SMALL, V_PLAN, -EINVAL}, {V_OUTMAX, V_IN, -EINVAL},
+};
+
 int main() {
     if (args_check() || args_big_product() || args_pairs() || outputs_check() || geometry_check() || lds_check() ||
-        group_check())
+        group_check() || pairs_check(kChanPairs, good(), chan_args, &lphy_chan_plan::decim, &lphy_chan_plan::out_stride))
         return 1;
     std::printf("channelize_check: ok kChanTile=%u sizeof(lphy_chan_plan)=%zu\n", kChanTile, sizeof(lphy_chan_plan));
     return 0;

@@ -1,5 +1,5 @@
 // Stand-alone program over the host-compilable part of the synthesiser
-// (csrc/lphy_synth_plan.h), for a run under the host sanitizers
+// (csrc/lphy_resample_plan.h), for a run under the host sanitizers
 // (tests/test_synthesize_cpu.py):
 //   - every row of synth_args in the documented order, pairs of bad arguments
 //     (the earlier row wins), and the overflow-prone rows at 2^32, 2^48, 2^64;
@@ -10,12 +10,13 @@
 //     are the definition's 64-bit ones, and the slot is staged (synth_stage,
 //     synth_slot_sample) as sample j when 0 <= j < in_samples and as zero
 //     otherwise;
-//   - synth_group, synth_lds_bytes and synth_lds_path.
+//   - res_group, synth_lds_bytes and synth_lds_path.
 // Prints the tile, sizeof(lphy_synth_plan) and its members' offsets.
 #include <cstdio>
 #include <initializer_list>
 
-#include "lphy_synth_plan.h"
+#include "lphy_resample_plan.h"
+#include "resample_pairs.h"
 
 using namespace lphy;
 
@@ -80,11 +81,11 @@ static int args_check() {
     EXPECT(synth_args(true, &p, false, false, false, true) == -EINVAL);
     p.channels = 65;
     EXPECT(synth_args(true, &p, true, false, false, true) == -ERANGE);
-    // synth_aligned: any of the four off an 8-byte boundary, null pointers pass
+    // res_aligned: any of the four off an 8-byte boundary, null pointers pass
     alignas(16) static char buf[32];
-    EXPECT(synth_aligned(buf, buf + 8, buf + 16, nullptr) && synth_aligned(nullptr, buf, buf, buf + 24));
-    EXPECT(!synth_aligned(buf + 4, buf, buf, buf) && !synth_aligned(buf, buf + 4, buf, buf));
-    EXPECT(!synth_aligned(buf, buf, buf + 2, buf) && !synth_aligned(buf, buf, buf, buf + 1));
+    EXPECT(res_aligned(buf, buf + 8, buf + 16, nullptr) && res_aligned(nullptr, buf, buf, buf + 24));
+    EXPECT(!res_aligned(buf + 4, buf, buf, buf) && !res_aligned(buf, buf + 4, buf, buf));
+    EXPECT(!res_aligned(buf, buf, buf + 2, buf) && !res_aligned(buf, buf, buf, buf + 1));
 
     // the -ERANGE rows, each at its edge, in order
     p = good(), p.channels = 64;
@@ -176,8 +177,8 @@ static int outputs_check() {
 }
 
 static int geometry_check() {
-    EXPECT(synth_tiles(0) == 0 && synth_tiles(1) == 1 && synth_tiles(kSynthTile) == 1);
-    EXPECT(synth_tiles(kSynthTile + 1) == 2 && synth_tiles((uint64_t(1) << 32) - 1) == (uint64_t(1) << 32) / kSynthTile);
+    EXPECT(res_tiles(0) == 0 && res_tiles(1) == 1 && res_tiles(kSynthTile) == 1);
+    EXPECT(res_tiles(kSynthTile + 1) == 2 && res_tiles((uint64_t(1) << 32) - 1) == (uint64_t(1) << 32) / kSynthTile);
     EXPECT(synth_chain(1, 1) == 1 && synth_chain(5, 4) == 2 && synth_chain(4, 4) == 1 && synth_chain(3, 300) == 1);
     EXPECT(synth_chain(4096, 1) == 4096 && synth_chain(129, 16) == 9);
     unsigned long long reads = 0;
@@ -189,7 +190,7 @@ static int geometry_check() {
                                    (uint64_t(1) << 48) - 1000})
                 for (uint64_t outputs : {uint64_t(1), uint64_t(kSynthTile - 1), uint64_t(kSynthTile),
                                          uint64_t(kSynthTile + 1), uint64_t(2 * kSynthTile + 77)}) {
-                    for (uint64_t tile = 0; tile < synth_tiles(outputs); ++tile) {
+                    for (uint64_t tile = 0; tile < res_tiles(outputs); ++tile) {
                         const SynthSpan sp = synth_tile_span(first, U, T, outputs, tile);
                         const SynthStage stg = synth_stage(sp);
                         EXPECT(stg.zeros <= sp.samples && (stg.zeros == 0 || stg.j0 == 0));
@@ -206,7 +207,7 @@ static int geometry_check() {
                                 if (have) EXPECT(got == (uint64_t)j);
                             }
                         EXPECT(sp.nout >= 1 && sp.nout <= kSynthTile);
-                        EXPECT(tile * kSynthTile + sp.nout == (tile + 1 == synth_tiles(outputs) ? outputs : (tile + 1) * kSynthTile));
+                        EXPECT(tile * kSynthTile + sp.nout == (tile + 1 == res_tiles(outputs) ? outputs : (tile + 1) * kSynthTile));
                         EXPECT(sp.samples >= 1 && sp.samples <= S);
                         const uint64_t w0 = first + tile * kSynthTile;
                         EXPECT(sp.q0 == w0 / U && sp.p0 == w0 % U);
@@ -258,19 +259,35 @@ static int geometry_check() {
 }
 
 static int group_check() {
-    EXPECT(synth_group(1) == 1 && synth_group(2) == 2 && synth_group(3) == 4 && synth_group(4) == 4);
-    EXPECT(synth_group(5) == 8 && synth_group(8) == 8 && synth_group(9) == 8 && synth_group(64) == 8);
+    EXPECT(res_group(1) == 1 && res_group(2) == 2 && res_group(3) == 4 && res_group(4) == 4);
+    EXPECT(res_group(5) == 8 && res_group(8) == 8 && res_group(9) == 8 && res_group(64) == 8);
     EXPECT(synth_lds_bytes(1, 16, 129) == (16 + 9 + 1) * 8 && synth_lds_bytes(9, 16, 129) == 8 * (16 + 9 + 1) * 8);
     // the size rule: one channel always fits, eight channels do up to S = 1024
     EXPECT(synth_lds_path(1, 1, 4096) && synth_lds_bytes(1, 1, 4096) == (256 + 4096 + 1) * 8);
-    EXPECT(synth_lds_path(8, 1, 767) && synth_lds_bytes(8, 1, 767) == kSynthLdsBytes);
+    EXPECT(synth_lds_path(8, 1, 767) && synth_lds_bytes(8, 1, 767) == kResLdsBytes);
     EXPECT(!synth_lds_path(8, 1, 768) && !synth_lds_path(64, 1, 1025) && synth_lds_path(4, 1, 1025));
     EXPECT(synth_lds_path(64, 2, 1025) && !synth_lds_path(2, 1, 4096) && synth_lds_path(64, 16, 4096));
     return 0;
 }
 
+// two violations at once, one row per adjacent pair of synth_args's tests and some across the two codes
+static const Pair kSynthPairs[] = {
+    {V_CTX, V_PLAN, -EINVAL}, {V_PLAN, V_TABLES, -EINVAL}, {V_TABLES, V_OUT, -EINVAL}, {V_OUT, V_IN, -EINVAL},
+    {V_IN, V_ALIGN, -EINVAL}, {V_ALIGN, V_RES0, -EINVAL}, {V_RES0, V_RES1, -EINVAL}, {V_RES1, V_CH0, -EINVAL},
+    {V_CH0, V_T0, -EINVAL}, {V_T0, V_STEP0, -EINVAL}, {V_STEP0, V_R0, -EINVAL}, {V_R0, V_CHMAX, -EINVAL},
+    {V_CHMAX, V_TMAX, -ERANGE}, {V_TMAX, V_STEPMAX, -ERANGE}, {V_STEPMAX, V_RMAX, -ERANGE},
+    {V_RMAX, V_OUTMAX, -ERANGE}, {V_OUTMAX, V_STRIDE_SMALL, -ERANGE}, {V_STRIDE_SMALL, V_INMAX, -ERANGE},
+    {V_INMAX, V_STRIDE_BIG, -ERANGE}, {V_STRIDE_BIG, V_FIRST, -ERANGE}, {V_CHMAX, V_RES0, -EINVAL},
+    {V_INMAX, V_STRIDE_SMALL, -ERANGE}, {V_CHMAX, V_ALIGN, -EINVAL}, {V_OUTMAX, V_RES1, -EINVAL},
+    {V_STRIDE_BIG, V_R0, -EINVAL}, {V_INMAX, V_OUT, -EINVAL}, {V_FIRST, V_CTX, -EINVAL}, {V_STEPMAX, V_T0, -EINVAL},
+    {V_STRIDE_BIG, V_TABLES, -EINVAL}, {V_RMAX, V_IN, -EINVAL}, {V_FIRST, V_STEP0, -EINVAL}, {V_TMAX, V_CH0, -EINVAL},
+    {V_STRIDE_SMALL, V_PLAN, -EINVAL}, {V_OUTMAX, V_IN, -EINVAL},
+};
+
 int main() {
-    if (args_check() || outputs_check() || geometry_check() || group_check()) return 1;
+    if (args_check() || outputs_check() || geometry_check() || group_check() ||
+        pairs_check(kSynthPairs, good(), synth_args, &lphy_synth_plan::interp, &lphy_synth_plan::in_stride))
+        return 1;
     static_assert(sizeof(lphy_synth_plan) == 64, "lphy_synth_plan is 64 bytes");
     std::printf("synthesize_check: ok kSynthTile=%u sizeof(lphy_synth_plan)=%zu offsets=%zu,%zu,%zu,%zu,%zu,%zu,%zu,%zu,%zu,%zu\n",
                 kSynthTile, sizeof(lphy_synth_plan), offsetof(lphy_synth_plan, first),

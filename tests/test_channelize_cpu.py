@@ -1,35 +1,27 @@
 """The channeliser without a device: the host-compilable part of it
-(csrc/lphy_chan_plan.h: argument check, output count, tile geometry, LDS image)
+(csrc/lphy_resample_plan.h: argument check, output count, tile geometry, LDS image)
 as a stand-alone program under ASan + UBSan (tests/cpp/channelize_check.cpp),
 the binding's constants against the headers, the numpy model of the definition
 (tests/channelize_model.py) against tables written out by hand, and the design
 helper lphy.chan_design against the model's own float64 maths."""
 import re
-import subprocess
 from fractions import Fraction as F
 from pathlib import Path
 
 import numpy as np
 import pytest
 
+import hostcc
 import channelize_model as model
 
 ROOT = Path(__file__).resolve().parents[1]
-CPP = ROOT / "tests" / "cpp"
 PKG = ROOT / "lora-sdr-lightweight-standalone-library-clean_amd"
 CSRC = PKG / "csrc"
 
 
 @pytest.fixture(scope="module")
 def check_output(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("channelize") / "channelize_check"
-    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-fsanitize=address,undefined",
-                        "-fno-sanitize-recover=all", "-I", str(CSRC), "-o", str(exe),
-                        str(CPP / "channelize_check.cpp")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    return r.stdout.strip()
+    return hostcc.run_check("channelize_check.cpp", tmp_path_factory.mktemp("channelize")).strip()
 
 
 def test_plan_logic_under_the_host_sanitizers(check_output):
@@ -40,8 +32,8 @@ def test_binding_knows_the_tile_and_the_plan(check_output):
     """lphy.CHAN_TILE, which the device tests place their edges by, is the
     header's, and CHAN_PLAN is lphy_chan_plan as the C compiler lays it out."""
     import lphy
-    text = (CSRC / "lphy_chan_plan.h").read_text()
-    assert int(re.search(r"kChanTile = (\d+);", text).group(1)) == lphy.CHAN_TILE
+    text = (CSRC / "lphy_resample_plan.h").read_text()
+    assert int(re.search(r"kResTile = (\d+);", text).group(1)) == lphy.CHAN_TILE
     tile, size = (int(x) for x in re.findall(r"=(\d+)", check_output))
     assert tile == lphy.CHAN_TILE and size == lphy.CHAN_PLAN.itemsize == 64
     p = lphy.chan_plan(first=1, in_samples=2, outputs=3, out_stride=4, rot_first=5, channels=6, taps=7, decim=8,

@@ -7,40 +7,30 @@ reduced masks against the unreduced walk, the positions around INT_MAX in 64
 bits, and the masks of the first 4096 positions against the oracle's whitening
 (pinned to the reference header by tests/test_oracle_vs_reference.py)."""
 import re
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
-ROOT = Path(__file__).resolve().parents[1]
-CPP = ROOT / "tests" / "cpp"
-CSRC = ROOT / "lora-sdr-lightweight-standalone-library-clean_amd" / "csrc"
+import hostcc
 
 
 @pytest.fixture(scope="module")
-def exe(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("codes_plan") / "codes_plan_check"
-    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-fsanitize=address,undefined",
-                        "-fno-sanitize-recover=all", "-I", str(CSRC), "-o", str(exe),
-                        str(CPP / "codes_plan_check.cpp")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return exe
+def check(tmp_path_factory):
+    """codes_plan_check.cpp's output for the given arguments; built on the first call"""
+    tmp = tmp_path_factory.mktemp("codes_plan")
+    return lambda *args: hostcc.run_check("codes_plan_check.cpp", tmp, *args, timeout=120)
 
 
-def test_periods_and_reduction_under_the_host_sanitizers(exe):
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
-    m = re.fullmatch(r"codes_plan_check: ok periods=511,510,255 checked=(\d+)", r.stdout.strip())
-    assert m and int(m.group(1)) == 316456, r.stdout   # every comparison made: no loop came up empty
+def test_periods_and_reduction_under_the_host_sanitizers(check):
+    out = check()
+    m = re.fullmatch(r"codes_plan_check: ok periods=511,510,255 checked=(\d+)", out.strip())
+    assert m and int(m.group(1)) == 316456, out   # every comparison made: no loop came up empty
 
 
-def test_reduced_masks_equal_the_oracle(exe, oracle):
+def test_reduced_masks_equal_the_oracle(check, oracle):
     """Whitening zeros gives the masks themselves: 4096 positions (eight
     periods) of every kind and rdd, from bit_ofs 0 and from 777."""
-    r = subprocess.run([str(exe), "dump"], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
-    lines = r.stdout.splitlines()
+    lines = check("dump").splitlines()
     assert len(lines) == 3 * 5 * 2
     seen = set()
     for line in lines:

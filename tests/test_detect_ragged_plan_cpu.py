@@ -7,17 +7,13 @@ for the other plans."""
 import ctypes as C
 import errno
 import itertools
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
+import hostcc
 from test_estimate_ragged_cpu import _mod_scratch
 
-ROOT = Path(__file__).resolve().parents[1]
-CPP = ROOT / "tests" / "cpp"
-CSRC = ROOT / "lora-sdr-lightweight-standalone-library-clean_amd" / "csrc"
 
 IN, OUT = 1, 2
 REC, DESC, IQ = 16, 32, 8
@@ -25,11 +21,7 @@ REC, DESC, IQ = 16, 32, 8
 
 @pytest.fixture(scope="module")
 def lib(tmp_path_factory):
-    d = tmp_path_factory.mktemp("detect_ragged_plan")
-    so = d / "libdetect_ragged_plan_check.so"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-fPIC", "-shared", "-I", str(CSRC), "-o", str(so),
-                    str(CPP / "detect_ragged_plan_check.cpp")], check=True)
-    L = C.CDLL(str(so))
+    L = hostcc.shared_lib("detect_ragged_plan_check.cpp", tmp_path_factory.mktemp("detect_ragged_plan"))
     L.detect_ragged_plan_check.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]
     L.detect_ragged_reserve_check.argtypes = [C.c_uint64] * 5
     L.detect_ragged_reserve_check.restype = C.c_uint64

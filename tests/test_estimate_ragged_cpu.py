@@ -7,16 +7,12 @@ does for the other plans; and the binding's argument checks."""
 import ctypes as C
 import errno
 import itertools
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = Path(__file__).resolve().parents[1]
-CPP = ROOT / "tests" / "cpp"
-CSRC = ROOT / "lora-sdr-lightweight-standalone-library-clean_amd" / "csrc"
+import hostcc
 
 IN, INOUT = 1, 3
 META, DESC, IQ = 32, 32, 8
@@ -24,11 +20,7 @@ META, DESC, IQ = 32, 32, 8
 
 @pytest.fixture(scope="module")
 def lib(tmp_path_factory):
-    d = tmp_path_factory.mktemp("estimate_ragged_plan")
-    so = d / "libestimate_ragged_plan_check.so"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-fPIC", "-shared", "-I", str(CSRC), "-o", str(so),
-                    str(CPP / "estimate_ragged_plan_check.cpp")], check=True)
-    L = C.CDLL(str(so))
+    L = hostcc.shared_lib("estimate_ragged_plan_check.cpp", tmp_path_factory.mktemp("estimate_ragged_plan"))
     L.estimate_ragged_plan_check.argtypes = [C.c_uint64, C.c_uint64, C.c_void_p]
     L.estimate_ragged_reserve_check.argtypes = [C.c_uint64] * 5
     L.estimate_ragged_reserve_check.restype = C.c_uint64

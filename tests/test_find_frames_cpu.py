@@ -4,27 +4,21 @@ stand-alone program under ASan + UBSan (tests/cpp/find_frames_check.cpp), and
 the numpy model of the definition (tests/find_frames_model.py) against three
 tables written out by hand."""
 import re
-import subprocess
 from pathlib import Path
 
 import numpy as np
 
+import hostcc
 import find_frames_model as model
 
 ROOT = Path(__file__).resolve().parents[1]
-CPP = ROOT / "tests" / "cpp"
 PKG = ROOT / "lora-sdr-lightweight-standalone-library-clean_amd"
 CSRC = PKG / "csrc"
 
 
 def test_scan_logic_under_the_host_sanitizers(tmp_path):
-    exe = tmp_path / "find_frames_check"
-    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-fsanitize=address,undefined",
-                        "-fno-sanitize-recover=all", "-I", str(CSRC), "-o", str(exe),
-                        str(CPP / "find_frames_check.cpp")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stdout.strip() == "find_frames_check: ok", r.stdout + r.stderr
+    out = hostcc.run_check("find_frames_check.cpp", tmp_path)
+    assert out.strip() == "find_frames_check: ok", out
 
 
 def test_binding_knows_the_tile():

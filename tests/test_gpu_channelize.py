@@ -10,28 +10,11 @@ import numpy as np
 import pytest
 
 import channelize_model as model
+from resample_helpers import BIG, EINVAL, ERANGE, _u8, dem, guarded, rand_c64, unguarded  # noqa: F401 (dem: a fixture)
 
 pytestmark = pytest.mark.gpu
 
-EINVAL, ERANGE = -22, -34
-GUARD = 4      # samples in front of and behind the output, which the call must leave alone
 PAD = 3        # out_stride = outputs + PAD
-BIG = (1 << 40) + 3
-
-
-@pytest.fixture(scope="module")
-def dem(lphy):
-    d = lphy.Demodulator(7)
-    yield d
-    d.close()
-
-
-def _u8(a):
-    return np.ascontiguousarray(a).view(np.uint8)
-
-
-def rand_c64(rng, *shape):
-    return (rng.standard_normal(shape) + 1j * rng.standard_normal(shape)).astype(np.complex64)
 
 
 def inputs(seed, C_, T, D, n_out, first, R, extra=2):
@@ -60,14 +43,11 @@ def device_call(lphy, d, x, taps, rot, D, first, n_out, rot_first, fill=0xA5, of
         assert t_x.data_ptr() % 16 == 0
     t_taps = torch.from_numpy(taps.view(np.float32).copy()).to(dev)
     t_rot = torch.from_numpy(rot.view(np.float32).copy()).to(dev)
-    t_out = torch.full(((C_ * stride + 2 * GUARD) * 8,), fill, dtype=torch.uint8, device=dev)
+    t_all_out, t_out = guarded(dev, C_ * stride * 8, fill)
     plan = lphy.chan_plan(first, x.size if in_samples is None else in_samples, n_out, stride, rot_first, C_, T, D, R)
-    d.channelize(t_x, plan, t_taps, t_rot, t_out[GUARD * 8: (GUARD + C_ * stride) * 8],
-                 stream=torch.cuda.current_stream().cuda_stream)
+    d.channelize(t_x, plan, t_taps, t_rot, t_out, stream=torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
-    out = t_out.cpu().numpy()
-    assert (out[: GUARD * 8] == fill).all() and (out[(GUARD + C_ * stride) * 8:] == fill).all(), "guards written"
-    return out[GUARD * 8: (GUARD + C_ * stride) * 8].view(np.complex64).reshape(C_, stride).copy()
+    return unguarded(t_all_out, C_ * stride * 8, fill).view(np.complex64).reshape(C_, stride).copy()
 
 
 def assert_output(got, want, n_out, fill, what):

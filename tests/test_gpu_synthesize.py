@@ -7,38 +7,21 @@ call does not depend on it (SF 7 here).
 
 K = lphy.SYNTH_TILE outputs make a tile.  A plan takes the LDS path when one
 channel group's staged samples fit 64 KiB (lds_path below, the rule of
-csrc/lphy_synth_plan.h; tests/cpp/synthesize_check.cpp pins its edge)."""
+csrc/lphy_resample_plan.h; tests/cpp/synthesize_check.cpp pins its edge)."""
 import numpy as np
 import pytest
 
 import synthesize_model as model
+from resample_helpers import BIG, EINVAL, ERANGE, _u8, dem, guarded, rand_c64, unguarded  # noqa: F401 (dem: a fixture)
 
 pytestmark = pytest.mark.gpu
 
-EINVAL, ERANGE = -22, -34
-GUARD = 4      # samples in front of and behind the output, which the call must leave alone
 PAD = 3        # in_stride = in_samples + PAD
-BIG = (1 << 40) + 3
 FILL = 0xA5
 
 
-@pytest.fixture(scope="module")
-def dem(lphy):
-    d = lphy.Demodulator(7)
-    yield d
-    d.close()
-
-
-def _u8(a):
-    return np.ascontiguousarray(a).view(np.uint8)
-
-
-def rand_c64(rng, *shape):
-    return (rng.standard_normal(shape) + 1j * rng.standard_normal(shape)).astype(np.complex64)
-
-
 def lds_bytes(lphy, C_, U, T):
-    """synth_lds_bytes of csrc/lphy_synth_plan.h."""
+    """synth_lds_bytes of csrc/lphy_resample_plan.h."""
     group = 1
     while group < 8 and group < C_:
         group *= 2
@@ -47,7 +30,7 @@ def lds_bytes(lphy, C_, U, T):
 
 
 def lds_path(lphy, C_, U, T):
-    """synth_lds_path of csrc/lphy_synth_plan.h."""
+    """synth_lds_path of csrc/lphy_resample_plan.h."""
     return lds_bytes(lphy, C_, U, T) <= 64 * 1024
 
 
@@ -82,9 +65,7 @@ def device_call(lphy, d, x, taps, rot, U, first, n_out, rot_first, fill=FILL, of
     t_x.copy_(torch.from_numpy(xf.copy()))
     t_taps = torch.from_numpy(taps.view(np.float32).copy()).to(dev)
     t_rot = torch.from_numpy(rot.view(np.float32).copy()).to(dev)
-    t_out = torch.full(((n_out + 2 * GUARD + (1 if offset8 else 0)) * 8,), fill, dtype=torch.uint8, device=dev)
-    g0 = (GUARD + (1 if offset8 else 0)) * 8
-    o = t_out[g0: g0 + n_out * 8]
+    t_out, o = guarded(dev, n_out * 8, fill, lead=8 if offset8 else 0)
     assert t_all.data_ptr() % 16 == 0 and t_out.data_ptr() % 16 == 0
     if offset8:
         assert t_x.data_ptr() % 16 == 8 and (o.data_ptr() % 16 == 8 or n_out == 0)
@@ -92,11 +73,10 @@ def device_call(lphy, d, x, taps, rot, U, first, n_out, rot_first, fill=FILL, of
     s = torch.cuda.current_stream().cuda_stream if stream is None else stream
     d.synthesize(t_x[2 * skip:], plan, t_taps, t_rot, o, stream=s)
     torch.cuda.synchronize()
-    out = t_out.cpu().numpy()
-    assert (out[:g0] == fill).all() and (out[g0 + n_out * 8:] == fill).all(), "guards written"
+    out = unguarded(t_out, n_out * 8, fill, lead=8 if offset8 else 0)
     assert t_x.cpu().numpy().tobytes() == xf.tobytes(), "streams written"
     assert t_taps.cpu().numpy().tobytes() == taps.tobytes() and t_rot.cpu().numpy().tobytes() == rot.tobytes()
-    return out[g0: g0 + n_out * 8].view(np.complex64).copy()
+    return out.view(np.complex64).copy()
 
 
 def assert_equal(got, want, what):
@@ -186,13 +166,11 @@ def test_no_input_sample_at_all(lphy, dem):
     taps, rot = rand_c64(np.random.default_rng(1), 3, 5), rand_c64(np.random.default_rng(2), 3, 7)
     t_taps = torch.from_numpy(taps.view(np.float32).copy()).to(dev)
     t_rot = torch.from_numpy(rot.view(np.float32).copy()).to(dev)
-    t_out = torch.full(((K + 1 + 2 * GUARD) * 8,), FILL, dtype=torch.uint8, device=dev)
-    dem.synthesize(None, lphy.synth_plan(3, 0, 0, K + 1, 0, 3, 5, 2, 7), t_taps, t_rot,
-                   t_out[GUARD * 8: (GUARD + K + 1) * 8], stream=torch.cuda.current_stream().cuda_stream)
+    t_out, o = guarded(dev, (K + 1) * 8, FILL)
+    dem.synthesize(None, lphy.synth_plan(3, 0, 0, K + 1, 0, 3, 5, 2, 7), t_taps, t_rot, o,
+                   stream=torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
-    out = t_out.cpu().numpy()
-    assert (out[:GUARD * 8] == FILL).all() and (out[(GUARD + K + 1) * 8:] == FILL).all()
-    assert (out[GUARD * 8: (GUARD + K + 1) * 8] == 0).all()
+    assert (unguarded(t_out, (K + 1) * 8, FILL) == 0).all()
 
 
 @pytest.mark.parametrize("C_, U, T, first", [(3, 8, 129, 3), (8, 1, 5, 0), (2, 3, 5, 1), (8, 1, 1025, 2)])

@@ -25,29 +25,17 @@ import pytest
 
 import channelize_model
 import synthesize_model as model
+from resample_helpers import frames_of, rx_buffers
 
 pytestmark = pytest.mark.gpu
 
 SF, N, U, T = 7, 128, 8, 129
 CENTRES = [F(-3, 10), F(1, 10), F(3, 10)]
 CUTOFF, BETA = 0.09, 8.0
-PAYLOAD_LENS = [[1, 5, 2], [3, 1, 4], [5, 2, 3]]   # per channel
 GAPS = [[3, 2, 4], [2, 5, 2], [4, 3, 3]]           # symbols of silence in front of each frame
 SYMBOLS = 80                                        # per channel stream
 MAX_FRAMES = 5
 FILL = 0xEE
-
-
-def frames_of(oracle, ch):
-    """Channel ch's frames: header, payload, checksum."""
-    rng = np.random.default_rng(7000 + ch)
-    out = []
-    for n in PAYLOAD_LENS[ch]:
-        body = rng.integers(0, 256, n, dtype=np.uint8)
-        crc = int(oracle.sx_checksum(body))
-        out.append(np.concatenate([rng.integers(0, 256, 2, dtype=np.uint8), body,
-                                   np.array([crc & 0xFF, crc >> 8], np.uint8)]))
-    return out
 
 
 def places_of(frames, ch):
@@ -127,14 +115,7 @@ def test_tx_to_rx_over_the_wideband_stream(lphy, setup):
             tx.append(dict(data=torch.from_numpy(np.concatenate(frames)).to(dev),
                            desc=torch.from_numpy(desc.view(np.uint8).copy()).to(dev),
                            bytes=int(sum(f.size for f in frames))))
-            per.append(dict(
-                rec=torch.full((windows * 16,), FILL, dtype=torch.uint8, device=dev),
-                desc=torch.full(((MAX_FRAMES + 1) * 32,), FILL, dtype=torch.uint8, device=dev),
-                info=torch.full((32,), FILL, dtype=torch.uint8, device=dev),
-                work=torch.full((d.find_frames_workspace(windows),), FILL, dtype=torch.uint8, device=dev),
-                syms=torch.full((n_sym,), -1, dtype=torch.int16, device=dev),
-                data=torch.full((n_sym // 2 + 1,), FILL, dtype=torch.uint8, device=dev),
-                meta=torch.full((MAX_FRAMES * 32,), FILL, dtype=torch.uint8, device=dev)))
+            per.append(rx_buffers(d, dev, windows, n_sym, MAX_FRAMES, FILL))
         # everything below is enqueued on the one stream; the host reads nothing until the end
         for ch, b in enumerate(tx):
             d.tx_ragged(b["data"], b["desc"], 3, t_tx[ch * n * 2: (ch + 1) * n * 2], stream=s.cuda_stream,

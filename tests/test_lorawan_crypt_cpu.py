@@ -9,18 +9,16 @@ tests/cpp/lorawan_crypt_check.cpp, and called through ctypes):
 * the same helpers as a stand-alone program under ASan + UBSan;
 * the binding names the four entry points."""
 import ctypes as C
-import subprocess
 from pathlib import Path
 
 import numpy as np
 import pytest
 
+import hostcc
 from lorawan_crypt_model import block_a
 
 ROOT = Path(__file__).resolve().parents[1]
-CPP = ROOT / "tests" / "cpp"
 PKG = ROOT / "lora-sdr-lightweight-standalone-library-clean_amd"
-CSRC = PKG / "csrc"
 
 DESC = np.dtype([("iq_offset", "<u8"), ("samples", "<u8"), ("sym_offset", "<u8"), ("unit_offset", "<u8")])
 EINVAL, ERANGE, ENOKEY = -22, -34, -126
@@ -29,11 +27,7 @@ JOB = ("status", "offset", "len", "devaddr", "fcnt", "key", "uplink")
 
 @pytest.fixture(scope="module")
 def lib(tmp_path_factory):
-    d = tmp_path_factory.mktemp("lorawan_crypt")
-    so = d / "liblorawan_crypt_check.so"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-fPIC", "-shared", "-I", str(CSRC), "-o", str(so),
-                    str(CPP / "lorawan_crypt_check.cpp")], check=True)
-    L = C.CDLL(str(so))
+    L = hostcc.shared_lib("lorawan_crypt_check.cpp", tmp_path_factory.mktemp("lorawan_crypt"))
     L.lw_crypt_block_check.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
     L.lw_crypt_block_check.restype = None
     L.lw_crypt_job_batch_check.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
@@ -160,15 +154,8 @@ def test_rx_front_end_ranges_and_status_order(lib, lphy):
 def test_front_ends_under_the_host_sanitizers(tmp_path):
     """The same source as a stand-alone program (-DLW_CRYPT_MAIN) under ASan +
     UBSan: the block and the three front ends on exactly-sized heap records."""
-    exe = tmp_path / "lorawan_crypt_san"
-    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-fsanitize=address,undefined",
-                        "-fno-sanitize-recover=all", "-DLW_CRYPT_MAIN", "-I", str(CSRC), "-o", str(exe),
-                        str(CPP / "lorawan_crypt_check.cpp")], capture_output=True, text=True)
-    if r.returncode != 0 and ("asan" in r.stderr or "ubsan" in r.stderr):
-        pytest.skip("g++ has no sanitizer runtimes here")
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stdout.strip() == "lorawan_crypt_check: ok", r.stdout + r.stderr
+    out = hostcc.run_check("lorawan_crypt_check.cpp", tmp_path, define="LW_CRYPT_MAIN", skip_without_sanitizers=True)
+    assert out.strip() == "lorawan_crypt_check: ok", out
 
 
 def test_binding_names_the_entry_points(lphy):

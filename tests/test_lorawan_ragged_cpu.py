@@ -13,16 +13,15 @@ tests/cpp/lorawan_ragged_check.cpp, and called through ctypes):
 * the binding names the new entry points and lays the records out as the header
   does."""
 import ctypes as C
-import subprocess
 from pathlib import Path
 
 import numpy as np
 import pytest
 
+import hostcc
+
 ROOT = Path(__file__).resolve().parents[1]
-CPP = ROOT / "tests" / "cpp"
 PKG = ROOT / "lora-sdr-lightweight-standalone-library-clean_amd"
-CSRC = PKG / "csrc"
 
 DESC = np.dtype([("iq_offset", "<u8"), ("samples", "<u8"), ("sym_offset", "<u8"), ("unit_offset", "<u8")])
 EINVAL, ERANGE = -22, -34
@@ -30,11 +29,7 @@ EINVAL, ERANGE = -22, -34
 
 @pytest.fixture(scope="module")
 def lib(tmp_path_factory):
-    d = tmp_path_factory.mktemp("lorawan_ragged")
-    so = d / "liblorawan_ragged_check.so"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-fPIC", "-shared", "-I", str(CSRC), "-o", str(so),
-                    str(CPP / "lorawan_ragged_check.cpp")], check=True)
-    L = C.CDLL(str(so))
+    L = hostcc.shared_lib("lorawan_ragged_check.cpp", tmp_path_factory.mktemp("lorawan_ragged"))
     L.lw_tx_layout_check.argtypes = [C.c_uint, C.c_uint, C.c_void_p, C.c_size_t, C.c_void_p]
     L.lw_plain_tx_layout_check.argtypes = [C.c_uint, C.c_uint, C.c_void_p, C.c_size_t, C.c_void_p]
     L.lw_sessions_check_check.argtypes = [C.c_void_p, C.c_size_t]
@@ -155,15 +150,8 @@ def test_byte_encoder_equals_the_hamming_table(lib, lphy):
 def test_host_helpers_under_the_host_sanitizers(tmp_path):
     """The same source as a stand-alone program (-DLW_RAGGED_MAIN) under ASan +
     UBSan: the two host-only helpers and the search on exactly-sized heap tables."""
-    exe = tmp_path / "lorawan_ragged_san"
-    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-fsanitize=address,undefined",
-                        "-fno-sanitize-recover=all", "-DLW_RAGGED_MAIN", "-I", str(CSRC), "-o", str(exe),
-                        str(CPP / "lorawan_ragged_check.cpp")], capture_output=True, text=True)
-    if r.returncode != 0 and ("asan" in r.stderr or "ubsan" in r.stderr):
-        pytest.skip("g++ has no sanitizer runtimes here")
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stdout.strip() == "lorawan_ragged_check: ok", r.stdout + r.stderr
+    out = hostcc.run_check("lorawan_ragged_check.cpp", tmp_path, define="LW_RAGGED_MAIN", skip_without_sanitizers=True)
+    assert out.strip() == "lorawan_ragged_check: ok", out
 
 
 def test_binding_names_and_record_layouts(lphy):

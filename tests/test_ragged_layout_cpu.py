@@ -12,26 +12,18 @@ the context's N * osr) is compiled into a host-only test library
   mode or a null pointer;
 * the extent check of a caller's table (the host form's)."""
 import ctypes as C
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
-ROOT = Path(__file__).resolve().parents[1]
-CPP = ROOT / "tests" / "cpp"
-CSRC = ROOT / "lora-sdr-lightweight-standalone-library-clean_amd" / "csrc"
+import hostcc
 
 DESC = np.dtype([("iq_offset", "<u8"), ("samples", "<u8"), ("sym_offset", "<u8"), ("unit_offset", "<u8")])
 
 
 @pytest.fixture(scope="module")
 def lib(tmp_path_factory):
-    d = tmp_path_factory.mktemp("ragged_layout")
-    so = d / "libragged_layout_check.so"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-fPIC", "-shared", "-I", str(CSRC), "-o", str(so),
-                    str(CPP / "ragged_layout_check.cpp")], check=True)
-    L = C.CDLL(str(so))
+    L = hostcc.shared_lib("ragged_layout_check.cpp", tmp_path_factory.mktemp("ragged_layout"))
     L.ragged_layout_check.argtypes = [C.c_uint, C.c_uint, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
     L.ragged_extent_check.argtypes = [C.c_uint, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
     L.ragged_desc_size.restype = C.c_size_t

@@ -8,25 +8,19 @@ unit_offset <= u and its frame is below `frames`; a unit past the table's
 total is not live and read record 0."""
 import ctypes as C
 import itertools
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
-ROOT = Path(__file__).resolve().parents[1]
-CPP = ROOT / "tests" / "cpp"
-CSRC = ROOT / "lora-sdr-lightweight-standalone-library-clean_amd" / "csrc"
+import hostcc
+
 STEP = 128  # N = 128, osr = 1
 IQ, SAMPLES, SYM, UNIT = range(4)  # lphy_ragged_desc's fields
 
 
 @pytest.fixture(scope="module")
 def lib(tmp_path_factory):
-    so = tmp_path_factory.mktemp("ragged_unit") / "libragged_unit_check.so"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-fPIC", "-shared", "-I", str(CSRC), "-o", str(so),
-                    str(CPP / "ragged_unit_check.cpp")], check=True)
-    L = C.CDLL(str(so))
+    L = hostcc.shared_lib("ragged_unit_check.cpp", tmp_path_factory.mktemp("ragged_unit"))
     L.ru_layout_check.argtypes = [C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p]
     L.ru_units_check.argtypes = [C.c_void_p, C.c_uint, C.c_uint64, C.c_uint64, C.c_size_t, C.c_void_p]
     L.ru_units_check.restype = None
@@ -115,10 +109,5 @@ def test_forged_tables_stay_inside(lib, which):
 def test_resolver_under_the_host_sanitizers(tmp_path):
     """The same source as a stand-alone program (-DRAGGED_UNIT_MAIN) under
     ASan + UBSan, on heap tables of exactly frames + 1 records."""
-    exe = tmp_path / "ragged_unit_san"
-    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-fsanitize=address,undefined",
-                        "-fno-sanitize-recover=all", "-DRAGGED_UNIT_MAIN", "-I", str(CSRC), "-o", str(exe),
-                        str(CPP / "ragged_unit_check.cpp")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stdout.strip() == "ragged_unit_check: ok", r.stdout + r.stderr
+    out = hostcc.run_check("ragged_unit_check.cpp", tmp_path, define="RAGGED_UNIT_MAIN")
+    assert out.strip() == "ragged_unit_check: ok", out

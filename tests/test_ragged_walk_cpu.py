@@ -24,15 +24,11 @@ The same source as a stand-alone program runs under ASan + UBSan."""
 import ctypes as C
 import errno
 import itertools
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
-ROOT = Path(__file__).resolve().parents[1]
-CPP = ROOT / "tests" / "cpp"
-CSRC = ROOT / "lora-sdr-lightweight-standalone-library-clean_amd" / "csrc"
+import hostcc
 
 IQ, SAMPLES, SYM, UNIT = range(4)  # lphy_ragged_desc's fields
 DEMOD, DETECT, ESTIMATE, TX, COMPENSATE = range(5)  # ragged_walk_check.cpp's callers (TX: modulate and tx)
@@ -42,10 +38,7 @@ UNTOUCHED = 0xABABABABABABABAB
 
 @pytest.fixture(scope="module")
 def lib(tmp_path_factory):
-    so = tmp_path_factory.mktemp("ragged_walk") / "libragged_walk_check.so"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-fPIC", "-shared", "-I", str(CSRC), "-o", str(so),
-                    str(CPP / "ragged_walk_check.cpp")], check=True)
-    L = C.CDLL(str(so))
+    L = hostcc.shared_lib("ragged_walk_check.cpp", tmp_path_factory.mktemp("ragged_walk"))
     L.rw_walk.argtypes = [C.c_int, C.c_uint64, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
     L.rw_args.argtypes = [C.c_int, C.c_void_p]
     return L
@@ -314,10 +307,5 @@ def test_argument_checks(lib, who):
 def test_walk_and_checks_under_the_host_sanitizers(tmp_path):
     """The same source as a stand-alone program (-DRAGGED_WALK_MAIN) under ASan + UBSan, on heap
     tables of exactly frames + 1 records."""
-    exe = tmp_path / "ragged_walk_san"
-    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-fsanitize=address,undefined",
-                        "-fno-sanitize-recover=all", "-DRAGGED_WALK_MAIN", "-I", str(CSRC), "-o", str(exe),
-                        str(CPP / "ragged_walk_check.cpp")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stdout.strip() == "ragged_walk_check: ok", r.stdout + r.stderr
+    out = hostcc.run_check("ragged_walk_check.cpp", tmp_path, define="RAGGED_WALK_MAIN")
+    assert out.strip() == "ragged_walk_check: ok", out

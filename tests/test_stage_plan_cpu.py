@@ -15,15 +15,11 @@ test library (tests/cpp/stage_plan_check.cpp) and called through ctypes:
   below the old formula."""
 import ctypes as C
 import itertools
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
-ROOT = Path(__file__).resolve().parents[1]
-CPP = ROOT / "tests" / "cpp"
-CSRC = ROOT / "lora-sdr-lightweight-standalone-library-clean_amd" / "csrc"
+import hostcc
 
 IN, OUT, INOUT, ZERO_OUT, SCRATCH = 1, 2, 3, 6, 8
 DEMOD, RAGGED, DETECT, DECODE, ESTIMATE, COMPENSATE, COMPENSATE_BATCH, MODULATE = range(8)
@@ -32,11 +28,7 @@ META, DESC, REC, SPEC, IQ = 32, 32, 16, 16, 8
 
 @pytest.fixture(scope="module")
 def lib(tmp_path_factory):
-    d = tmp_path_factory.mktemp("stage_plan")
-    so = d / "libstage_plan_check.so"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-fPIC", "-shared", "-I", str(CSRC), "-o", str(so),
-                    str(CPP / "stage_plan_check.cpp")], check=True)
-    L = C.CDLL(str(so))
+    L = hostcc.shared_lib("stage_plan_check.cpp", tmp_path_factory.mktemp("stage_plan"))
     L.stage_plan_check.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
     L.stage_reserve_check.argtypes = [C.c_uint64] * 5
     L.stage_reserve_check.restype = C.c_uint64

@@ -1,5 +1,5 @@
 """The synthesiser without a device: the host-compilable part of it
-(csrc/lphy_synth_plan.h: argument check, output count, tile geometry, LDS
+(csrc/lphy_resample_plan.h: argument check, output count, tile geometry, LDS
 image) as a stand-alone program under ASan + UBSan
 (tests/cpp/synthesize_check.cpp), the binding's constants and record layout
 against the headers, the argument errors from the shared library itself, the
@@ -9,31 +9,23 @@ model's own float64 maths and against lphy.chan_design."""
 import ctypes
 import errno
 import re
-import subprocess
 from fractions import Fraction as F
 from pathlib import Path
 
 import numpy as np
 import pytest
 
+import hostcc
 import synthesize_model as model
 
 ROOT = Path(__file__).resolve().parents[1]
-CPP = ROOT / "tests" / "cpp"
 PKG = ROOT / "lora-sdr-lightweight-standalone-library-clean_amd"
 CSRC = PKG / "csrc"
 
 
 @pytest.fixture(scope="module")
 def check_output(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("synthesize") / "synthesize_check"
-    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-fsanitize=address,undefined",
-                        "-fno-sanitize-recover=all", "-I", str(CSRC), "-o", str(exe),
-                        str(CPP / "synthesize_check.cpp")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    return r.stdout.strip()
+    return hostcc.run_check("synthesize_check.cpp", tmp_path_factory.mktemp("synthesize")).strip()
 
 
 def test_plan_logic_under_the_host_sanitizers(check_output):
@@ -46,8 +38,8 @@ def test_binding_knows_the_tile_and_the_plan(check_output):
     header's, and SYNTH_PLAN is lphy_synth_plan as the C compiler lays it out:
     size and every member's offset."""
     import lphy
-    text = (CSRC / "lphy_synth_plan.h").read_text()
-    assert int(re.search(r"kSynthTile = (\d+);", text).group(1)) == lphy.SYNTH_TILE
+    text = (CSRC / "lphy_resample_plan.h").read_text()
+    assert int(re.search(r"kResTile = (\d+);", text).group(1)) == lphy.SYNTH_TILE
     tile, size = (int(x) for x in re.findall(r"=(\d+)", check_output)[:2])
     offsets = [int(x) for x in check_output.rsplit("=", 1)[1].split(",")]
     assert tile == lphy.SYNTH_TILE and size == lphy.SYNTH_PLAN.itemsize == 64

@@ -13,15 +13,11 @@ checks of lphy_hip_tx_ragged_host (tx_extent) and its staging plan
   exactly the slices that go in and come out;
 * the reservation covers tx_plan at the reserved shape."""
 import ctypes as C
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
-ROOT = Path(__file__).resolve().parents[1]
-CPP = ROOT / "tests" / "cpp"
-CSRC = ROOT / "lora-sdr-lightweight-standalone-library-clean_amd" / "csrc"
+import hostcc
 
 DESC = np.dtype([("iq_offset", "<u8"), ("samples", "<u8"), ("sym_offset", "<u8"), ("unit_offset", "<u8")])
 EINVAL, ERANGE = -22, -34
@@ -30,11 +26,7 @@ IN, OUT, INOUT = 1, 2, 3
 
 @pytest.fixture(scope="module")
 def lib(tmp_path_factory):
-    d = tmp_path_factory.mktemp("tx_layout")
-    so = d / "libtx_layout_check.so"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-fPIC", "-shared", "-I", str(CSRC), "-o", str(so),
-                    str(CPP / "tx_layout_check.cpp")], check=True)
-    L = C.CDLL(str(so))
+    L = hostcc.shared_lib("tx_layout_check.cpp", tmp_path_factory.mktemp("tx_layout"))
     L.tx_layout_check.argtypes = [C.c_uint, C.c_uint, C.c_void_p, C.c_size_t, C.c_void_p]
     L.tx_ragged_layout_check.argtypes = [C.c_uint, C.c_uint, C.c_void_p, C.c_size_t, C.c_void_p]
     L.tx_extent_check.argtypes = [C.c_uint, C.c_uint, C.c_void_p, C.c_size_t, C.c_void_p]
