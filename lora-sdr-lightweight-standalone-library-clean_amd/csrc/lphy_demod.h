@@ -439,13 +439,8 @@ __device__ __forceinline__ cf32 rotate_sample(cf32 x, int i, const SymCtx& c,
     }
     const float ph = c.start + c.rate * (float)i;
     float sn, cs;
-#ifdef LPHY_ABLATE_SINCOS  // timing experiments only (tools/ubench/demod_ablate)
-    sn = ph; cs = 1.0f - ph;
-    (void)large;
-#else
     if (large) lphy_libm::sincosf_large(ph, &sn, &cs);
     else lphy_libm::sincosf_fast(ph, &sn, &cs);
-#endif
     x = cmul_t<AG>(x, cf32{cs, sn});
     if constexpr ((MODE & kWinBit) != 0) x = cscale(x, win[i]);
     return x;
@@ -524,18 +519,11 @@ __device__ __forceinline__ void iq_check(const DemodArgs& A, unsigned long long 
 // k_frames' IQ loads (each sample read once, the estimate symbols twice):
 // non-temporal, so the stream does not evict the partly written output
 // lines and the tables from L2 (as k_wave's IQ DMA, lphy_wave.h
-// LPHY_IQ_CPOL).  Same-box A/B (profiles/r5/ab_iq_nt.txt): SF 8 fused
+// kIqCpol).  Same-box A/B (profiles/r5/ab_iq_nt.txt): SF 8 fused
 // 0.999-1.012 -> 0.977-0.979 ms, SF 7 within noise; C1 WRITE_SIZE 33.0 ->
-// 12.6 MB per launch.  (-DLPHY_IQ_NT=0 for timing experiments only.)
-#ifndef LPHY_IQ_NT
-#define LPHY_IQ_NT 1
-#endif
+// 12.6 MB per launch.
 __device__ __forceinline__ cf32 ld_iq(const cf32* p) {
-#if LPHY_IQ_NT
     return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
 }
 
 __device__ __forceinline__ void store_symbol(const DemodArgs& A, const SymCtx& c, uint16_t idx) {
@@ -610,12 +598,8 @@ __device__ __forceinline__ float cert_bound(float rate, float start, float amax,
 // correctly rounded sqrtf's Newton fix-up cost ~20 VALU per symbol tile.
 // A NaN winner stays NaN and fails the comparison.
 __device__ __forceinline__ float cert_gap(const ArgMax2& b) {
-#ifdef LPHY_AB_SQRT_EXACT  // A/B timing only: the correctly rounded sqrtf
-    return sqrtf(b.v) * (1.0f - 8.0f * kU) - sqrtf(fmaxf(b.v2, 1e-30f)) * (1.0f + 8.0f * kU);
-#else
     return __builtin_amdgcn_sqrtf(b.v) * (1.0f - 12.0f * kU) -
            __builtin_amdgcn_sqrtf(fmaxf(b.v2, 1e-30f)) * (1.0f + 12.0f * kU);
-#endif
 }
 template <int SF>
 __device__ __forceinline__ bool fast_certified(const ArgMax2& b, const SymCtx& c, float amax,
@@ -812,27 +796,13 @@ __global__ __launch_bounds__(kTile, OCC) void k_demod(DemodArgs A) {
         const SymCtx nc = sym_ctx<OSR>(A, nlive ? nf : 0, nlive ? ns : 0, nlive, N, nm);
         if (nfw < nframes) {
             const cf32* nsrc = A.iq + (unsigned long long)nc.f * A.frame_samples + nc.base;
-#ifdef LPHY_ABLATE_LOAD  // timing experiments only
-            (void)nsrc;
-#pragma unroll
-            for (int e = 0; e < G::E; ++e) raw[e] = raw[e] * 0.999f + cf32{(float)e, (float)lam};
-#else
 #pragma unroll
             for (int e = 0; e < G::E; ++e) raw[e] = nsrc[(unsigned)(lam + e * G::LPS) * osr];
-#endif
         }
 
         cf32 v[16];
-#ifdef LPHY_ABLATE_FFT  // timing experiments only
-        {
-            const Stage<SF> st2(slot, lam);
-#pragma unroll
-            for (int e = 0; e < G::E; ++e) v[e] = lds_ld(lds, G::at8(st2.lb8, G::cpart(e * G::LPS) << 3));
-        }
-#else
         if (FASTB && fastb) fft_tile<SF, true>(v, lds, slot, lam, twl);
         else fft_tile<SF>(v, lds, slot, lam, twl);
-#endif
         if constexpr (FASTB) {
             if (fastb) {
 #ifdef LPHY_PROFILE_PHASES

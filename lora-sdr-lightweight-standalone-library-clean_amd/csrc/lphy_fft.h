@@ -265,13 +265,11 @@ struct PassGeo {
 template <int SF>
 __device__ __forceinline__ void team_sync() {
     if constexpr (Geo<SF>::LPS <= 64) {
-#ifdef LPHY_TEAM_WAIT  // experiments: drain the wave's LDS queue (7 % slower)
-        __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
-#else
         // a wave's LDS operations execute in issue order, so a team inside
         // one wavefront only needs compiler motion across the point stopped
+        // (draining the wave's LDS queue here, s_waitcnt lgkmcnt(0), measured
+        // 7 % slower)
         asm volatile("" ::: "memory");
-#endif
         __builtin_amdgcn_wave_barrier();
     } else {
         __syncthreads();
@@ -671,29 +669,20 @@ __device__ __forceinline__ unsigned med3_u32(unsigned a, unsigned b, unsigned c)
 template <int N>
 __device__ __forceinline__ unsigned dpp_row_shl_z(unsigned v) {
     static_assert(N >= 1 && N <= 15, "row_shl range");
-#ifdef LPHY_AB_DPP_OLD  // A/B timing only: the old-value form
-    return (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x100 | N, 0xF, 0xF, false);
-#else
     return (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0x100 | N, 0xF, 0xF, true);
-#endif
 }
 // Top two of {k1, k2, a, b} for distinct keys with k1 >= k2: the second
 // largest is max(k2, med3(k1, a, b)) (if k1 leads {k1, a, b}, the middle is
 // max(a, b); otherwise the middle is the larger of k1 and the other new
 // key, and k1 >= k2).  One v_max3_u32, one v_med3_u32 and one v_max_u32
-// per two keys, against a v_med3_u32 and a v_max_u32 per key.
+// per two keys, against a v_med3_u32 and a v_max_u32 per key (the one-key
+// form measured SF 7 fused 0.976 / 0.965 against 0.959 / 0.955 ms;
+// profiles/r4/ab_top2_sf7.txt).
 __device__ __forceinline__ void top2_pair(unsigned& k1, unsigned& k2, unsigned a, unsigned b) {
-#ifdef LPHY_AB_TOP2_SINGLE  // A/B timing only: one key at a time
-    k2 = med3_u32(k1, k2, a);
-    k1 = k1 > a ? k1 : a;
-    k2 = med3_u32(k1, k2, b);
-    k1 = k1 > b ? k1 : b;
-#else
     const unsigned m = med3_u32(k1, a, b);
     const unsigned t = k1 > a ? k1 : a;
     k1 = t > b ? t : b;
     k2 = k2 > m ? k2 : m;
-#endif
 }
 template <int SF, int OFF = Geo<SF>::LPS / 2>
 __device__ __forceinline__ void team_top2_keys(unsigned& k1, unsigned& k2) {
@@ -727,12 +716,8 @@ __device__ __forceinline__ ArgMax2 team_argmax2_keyed_first(const cf32 (&v)[16],
     }(), "bin_of separable in the lane and element digits");
     static_assert(G::E % 2 == 0, "keys taken in pairs");
     auto key_of = [&](int e) __attribute__((always_inline)) {
-#ifdef LPHY_KEY_FMA  // A/B: |X|^2 = fma(x, x, fl(y y)), scalar f32 (within cert_gap's 8 u)
-        const float m2 = __builtin_fmaf(v[e].x, v[e].x, v[e].y * v[e].y);
-#else
         const cf32 sq = v[e] * v[e];
         const float m2 = sq.x + sq.y;
-#endif
         return (__float_as_uint(m2) & ~15u) | (unsigned)e;
     };
     unsigned k1 = 0u, k2 = 0u;

@@ -116,9 +116,7 @@ __device__ __forceinline__ bool finalize_frame_regs(const FinalArgs& A, unsigned
 }
 
 __device__ __forceinline__ void finalize_frame(const FinalArgs& A, unsigned long long f) {
-#ifndef LPHY_AB_FINAL_MEM  // A/B timing only: the memory form for every row
     if (finalize_frame_regs(A, f)) return;
-#endif
     lphy_frame_meta m = A.meta[f];
     if (m.status != 0) return;
     if (A.set_sync && m.have_sync)

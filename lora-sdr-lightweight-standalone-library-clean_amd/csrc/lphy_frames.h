@@ -91,11 +91,7 @@ __device__ __forceinline__ float wave_maxabs(const DemodArgs& A, unsigned f, con
     // 32 and 33 within 1 %; round 2, with the samples staged in registers:
     // 8 spills 6 VGPRs where 16 spills 15, 4 % faster under speculation and
     // 1 % with the whole-frame scan)
-#ifdef LPHY_MAXABS_U
-    constexpr int U = LPHY_MAXABS_U;
-#else
     constexpr int U = 8;
-#endif
     // chirp index of sample 2 (b + 64 u + lane) for a round base b = 64 U r:
     // the 128 U r term vanishes mod N
     static_assert((128 * U) % N == 0, "chirp phase of the unrolled scan");
@@ -456,11 +452,7 @@ __global__ __launch_bounds__(kTile, OCC) void k_frames(FrameArgs P) {
     // That needs both estimate units of a frame in one tile (teams 2j and
     // 2j + 1): 2 LPS <= 64 lanes, i.e. SF <= 9.  At SF 10 a team is the
     // whole wave (EBT = 2 tiles per frame), so the scans stay.
-#ifdef LPHY_AB_EB_SCAN  // A/B timing only: the round-2 scans under speculation too
-    constexpr bool kEbMax = false;
-#else
     constexpr bool kEbMax = 2 * G::LPS <= 64;
-#endif
     auto scan_ahead = [&](unsigned nkind_, unsigned nfk_) {
         if constexpr ((MODE & 3) != LPHY_MODE_DEMODULATE) {
             if (kEbMax && spec) return;
@@ -470,11 +462,7 @@ __global__ __launch_bounds__(kTile, OCC) void k_frames(FrameArgs P) {
                 if (grp != m_seq) {
                     for (unsigned j = 0; j < F && grp * F + j < nk; ++j) {
                         const unsigned kk = grp * F + j;
-#ifdef LPHY_ABLATE_FRAME_SCAN  // timing experiments only
-                        const float m = 1.0f;
-#else
                         const float m = wave_maxabs<SF, MODE>(A, w + kk * W, down, spec ? 2u * N : 0u);
-#endif
                         if (lane == 0) ringmx[wv][slot_of(kk)] = m;
                     }
                     m_seq = grp;
@@ -658,9 +646,7 @@ __global__ __launch_bounds__(kTile, OCC) void k_frames(FrameArgs P) {
         // so each wave's compute segment ends, and its next loads go out,
         // sooner.  Same-box A/B: fused 1.037 -> 1.016 ms (three rounds;
         // priority over the transform alone: 1.021)
-#ifndef LPHY_AB_NO_PRIO  // A/B timing only
         __builtin_amdgcn_s_setprio(1);
-#endif
         if (emask) fft_tile<SF, false, false, true>(v, lds, slot, lam, twl);
         else fft_tile<SF, true, false, true>(v, lds, slot, lam, twl);
 
@@ -670,18 +656,12 @@ __global__ __launch_bounds__(kTile, OCC) void k_frames(FrameArgs P) {
         // symbols use; estimate units need the detector's exact argmax)
         ArgMax2 b2;
         if constexpr (G::LPS <= 16) {
-#ifdef LPHY_EXACT_TOP2  // A/B experiments: the exact top two everywhere
-            b2 = team_argmax2_first<SF>(local_argmax2<SF>(v, lam));
-#else
             if (emask) b2 = team_argmax2_first<SF>(local_argmax2<SF>(v, lam));
             else b2 = team_argmax2_keyed_first<SF>(v, lam);
-#endif
         } else {
             b2 = symbol_argmax2<SF>(local_argmax2<SF>(v, lam));
         }
-#ifndef LPHY_AB_NO_PRIO
         __builtin_amdgcn_s_setprio(0);
-#endif
         ArgMax best{b2.v, b2.i};
         if (emask) {
             // detector outputs of the estimate units (LoRaDetector.hpp:60-71)

@@ -159,9 +159,7 @@ __global__ void k_mark_recheck(lphy_frame_meta* meta, unsigned long long frames)
 // re-runs of a demodulation), a workgroup per 256 frames
 __global__ __launch_bounds__(kTile) void k_finalize(FinalArgs A) {
     __shared__ FinStage st;
-#ifndef LPHY_AB_FINAL_THREAD  // A/B timing only: a row per thread straight from memory
     if (blockDim.x == kTile && finalize_block(A, (unsigned long long)blockIdx.x * kTile, st)) return;
-#endif
     const unsigned long long f = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (f < A.frames) finalize_frame(A, f);
 }
@@ -941,9 +939,6 @@ int compensate_batch_impl(const lphy_hip_ctx* c, const float* d_in, float* d_out
 // holds mod_scratch_bytes(): the per-symbol start phases, and below
 // mod_walk_all_below symbols every sample's phase too.
 constexpr size_t mod_walk_all_below = 4096;
-#ifndef LPHY_MOD_FAST  // 0: the three-kernel few-symbol form only (A/B builds)
-#define LPHY_MOD_FAST 1
-#endif
 
 // k_mod_fast's dynamic LDS limit on the context's device, found once per
 // device: the device's LDS per workgroup less the kernel's static LDS
@@ -976,7 +971,7 @@ size_t mod_fast_lds(int device) {
 // k_mod_cand, k_mod_fast<true, 3>).
 int mod_form(const lphy_hip_ctx* c, size_t frames, size_t nsyms) {
     const size_t ns = nsyms + 2, nph = frames * ns;
-    if (!LPHY_MOD_FAST || nph >= mod_walk_all_below || ns > (size_t)kModFastSyms) return 0;
+    if (nph >=mod_walk_all_below || ns > (size_t)kModFastSyms) return 0;
     const size_t lds = ns * (((size_t)c->N * c->osr + 4) * sizeof(float) + kModFastWin);
     return lds <= mod_fast_lds(c->device) ? 1 : 2;
 }

@@ -106,9 +106,7 @@ int launch_demod_sf(const DemodArgs& A, hipStream_t st, bool prologue, bool symb
 
 // Waves per SIMD of k_frames: 2 (<= 256 VGPRs; its loop carries more state
 // than k_demod's and spills at 3).
-#ifndef LPHY_FRAMES_OCC  // experiments: -DLPHY_FRAMES_OCC=3
-#define LPHY_FRAMES_OCC 2
-#endif
+constexpr int kFramesOcc = 2;
 // Fused path, k_frames (lphy_frames.h).
 template <int SF>
 int launch_frames_sf(const DemodArgs& A, hipStream_t st) {
@@ -123,9 +121,9 @@ int launch_frames_sf(const DemodArgs& A, hipStream_t st) {
             P.A = A;
             constexpr unsigned WPB = kTile / 64;
             const unsigned blocks = persistent_grid(
-                resident_blocks<&k_frames<SF, MODE, LPHY_FRAMES_OCC>>(current_device()), (A.frames + WPB - 1) / WPB, 0);
+                resident_blocks<&k_frames<SF, MODE, kFramesOcc>>(current_device()), (A.frames + WPB - 1) / WPB, 0);
             P.waves = blocks * WPB;
-            hipLaunchKernelGGL((k_frames<SF, MODE, LPHY_FRAMES_OCC>), dim3(blocks), dim3(kTile), 0, st, P);
+            hipLaunchKernelGGL((k_frames<SF, MODE, kFramesOcc>), dim3(blocks), dim3(kTile), 0, st, P);
             HIP_OK(hipGetLastError());
             return 0;
         });

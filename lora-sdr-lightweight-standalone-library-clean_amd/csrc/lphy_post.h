@@ -381,10 +381,8 @@ __global__ __launch_bounds__(kTile) void k_post(DemodArgs A, FinalArgs F, int fi
         }
     }
     if (!fin) return;
-#ifndef LPHY_AB_FINAL_THREAD  // A/B timing only: a row per thread straight from memory
     if (fix) __syncthreads();  // the re-runs are done with the shared workspace
     if (finalize_block(F, (unsigned long long)blockIdx.x * kTile, L.fs)) return;
-#endif
     if (f < A.frames) finalize_frame(F, f);
 }
 

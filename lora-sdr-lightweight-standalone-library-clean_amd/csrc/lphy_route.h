@@ -10,15 +10,10 @@
 #include "../../include/lphy_hip.h"
 #include "lphy_testing.h"
 
-// (-D for timing experiments only)
-#ifndef LPHY_WAVE_MIN_SF  // smallest SF on k_wave
-#define LPHY_WAVE_MIN_SF 7
-#endif
-#ifndef LPHY_SPAN_MIN_SPW  // fewest symbols per k_wave unit for units spanning frames
-#define LPHY_SPAN_MIN_SPW 4
-#endif
-
 namespace lphy {
+
+constexpr unsigned kWaveMinSf = 7;  // smallest SF on k_wave
+constexpr int kSpanMinSpw = 4;      // fewest symbols per k_wave unit for units spanning frames
 
 // Separate: k_maxabs / k_estimate / k_demod, one launch each; Frames:
 // k_frames; Wave: k_wave, its units spanning frames or not (wave_spans)
@@ -37,13 +32,13 @@ constexpr bool frames_kernel(unsigned sf) { return route_lps(sf) >= 1 && route_l
 // k_wave's units span frames (WSchedSpan, SF 7-10) when a frame holds at
 // least one unit of symbols
 constexpr bool wave_spans(unsigned sf, size_t total_syms) {
-    return route_spw(sf) >= LPHY_SPAN_MIN_SPW && total_syms >= (size_t)route_spw(sf);
+    return route_spw(sf) >= kSpanMinSpw && total_syms >= (size_t)route_spw(sf);
 }
 // k_wave<SF, mode [| kWinBit], span> exists.  Not spanning: SF 9-12 only
 // (below, k_frames was 1.5x faster on frames shorter than a unit), and not
 // SF 12 mode 1 with the Hann window (it spilled 212 B per lane).
 constexpr bool wave_kernel(unsigned sf, int mode, bool window, bool span) {
-    if (span) return route_spw(sf) >= LPHY_SPAN_MIN_SPW;
+    if (span) return route_spw(sf) >= kSpanMinSpw;
     return route_spw(sf) != 0 && sf >= 9 && !(sf == 12 && window && mode == LPHY_MODE_LORA_DEMODULATE);
 }
 
@@ -69,7 +64,7 @@ inline Path route(const RouteArgs& r) {
         return Path::Separate;
     // k_wave: the certified rotation, in modes 1/2 the speculative
     // normalisation; LPHY_F_FRAMES_KERNEL (test build) keeps k_frames
-    if (r.sf >= LPHY_WAVE_MIN_SF && !(r.flags & LPHY_F_FRAMES_KERNEL) && !r.exact_rotation &&
+    if (r.sf >= kWaveMinSf && !(r.flags & LPHY_F_FRAMES_KERNEL) && !r.exact_rotation &&
         (r.mode == LPHY_MODE_DEMODULATE || r.spec) &&
         wave_kernel(r.sf, r.mode, r.window, wave_spans(r.sf, r.total_syms)))
         return Path::Wave;

@@ -61,22 +61,16 @@ namespace {
 // unroll of the LDS-DMA's run of shifted windows: 4 (the loop's counter,
 // compare and branch per 1 KiB piece were a third of a piece's ~8
 // instructions at SF 7, 32 pieces per unit; same-box A/B SF 7 fused
-// 0.785-0.801 -> 0.767-0.771 ms, SF 8-9 within noise).  (-D for timing
-// experiments only.)
-#ifndef LPHY_DMA_UNROLL
-#define LPHY_DMA_UNROLL 4
-#endif
+// 0.785-0.801 -> 0.767-0.771 ms, SF 8-9 within noise).
+constexpr int kDmaUnroll = 4;
 
 // cache policy of the IQ's LDS-DMA: nt (2), streaming. Every IQ line is
 // read once (twice for the estimate symbols), so it should not push the
 // twiddle table and the partly written output lines out of L2: same-box
 // A/B (profiles/r5/ab_iq_nt.txt) C2 1.63-1.69 -> 1.57-1.60 ms, FETCH
 // 1.044x -> 1.039x of the algorithmic bytes, WRITE 0.85 -> 0.66 MB (the
-// results exactly); SF 9 -1..2 %; sc1 (16): no change.  (-D for timing
-// experiments only.)
-#ifndef LPHY_IQ_CPOL
-#define LPHY_IQ_CPOL 2
-#endif
+// results exactly); SF 9 -1..2 %; sc1 (16): no change.
+constexpr int kIqCpol = 2;
 
 template <int SF>
 struct WGeo {
@@ -374,17 +368,14 @@ struct WTw {
 // per-lane table above and products with wave-uniform twiddles; exact: every
 // twiddle from the KISS table (per-lane loads, one butterfly group at a time).
 template <int SF, bool FAST>
-__device__ __forceinline__ void wpass2_s2(cf32 (&v)[64], const WTw<SF>& T, const cf32* __restrict__ tw, int l) {
+__device__ __forceinline__ void wpass2(cf32 (&v)[64], const WTw<SF>& T, const cf32* __restrict__ tw, int l) {
+    using W = WGeo<SF>;
     cf32 w2[3];
 #pragma unroll
     for (int q = 1; q <= 3; ++q) w2[q - 1] = FAST ? T.t2[q - 1] : tw[16 * l * q];
 #pragma unroll
     for (int b = 0; b < 16; ++b)
         wbfly4<FAST>(v[4 * b], v[4 * b + 1], v[4 * b + 2], v[4 * b + 3], w2[0], w2[1], w2[2], false);
-}
-template <int SF, bool FAST>
-__device__ __forceinline__ void wpass2_s10(cf32 (&v)[64], const WTw<SF>& T, const cf32* __restrict__ tw, int l) {
-    using W = WGeo<SF>;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         cfence();
@@ -411,11 +402,6 @@ __device__ __forceinline__ void wpass2_s10(cf32 (&v)[64], const WTw<SF>& T, cons
         }
         wbfly4<FAST>(v[r], v[r + 16], v[r + 32], v[r + 48], w[0], w[1], w[2], false);
     }
-}
-template <int SF, bool FAST>
-__device__ __forceinline__ void wpass2(cf32 (&v)[64], const WTw<SF>& T, const cf32* __restrict__ tw, int l) {
-    wpass2_s2<SF, FAST>(v, T, tw, l);
-    wpass2_s10<SF, FAST>(v, T, tw, l);
 }
 
 // The 64 x LPS transpose between the passes through the wave's buffer.
@@ -481,11 +467,11 @@ __device__ __forceinline__ void wdma(const DemodArgs& A, cf32* buf, const WDma& 
         for (int r = 0; r < W::PPS; r += 4) {
             g_void* g = (g_void*)(src + 128 * r);
             lds_void* ld = (lds_void*)(dst + 128 * r);
-            __builtin_amdgcn_global_load_lds(g, ld, 16, 0, LPHY_IQ_CPOL);
-            if constexpr (W::PPS >= 2) __builtin_amdgcn_global_load_lds(g, ld, 16, 1024, LPHY_IQ_CPOL);
+            __builtin_amdgcn_global_load_lds(g, ld, 16, 0, kIqCpol);
+            if constexpr (W::PPS >= 2) __builtin_amdgcn_global_load_lds(g, ld, 16, 1024, kIqCpol);
             if constexpr (W::PPS >= 4) {
-                __builtin_amdgcn_global_load_lds(g, ld, 16, 2048, LPHY_IQ_CPOL);
-                __builtin_amdgcn_global_load_lds(g, ld, 16, 3072, LPHY_IQ_CPOL);
+                __builtin_amdgcn_global_load_lds(g, ld, 16, 2048, kIqCpol);
+                __builtin_amdgcn_global_load_lds(g, ld, 16, 3072, kIqCpol);
             }
         }
     };
@@ -557,7 +543,7 @@ __device__ __forceinline__ void wdma(const DemodArgs& A, cf32* buf, const WDma& 
                 bound_check((long long)(sy0 + h) * N + t, (long long)count - N + 1);
                 bound_check((long long)(sy0 + hb - 1) * N + t, (long long)count - N + 1);
             }
-#pragma unroll LPHY_DMA_UNROLL
+#pragma unroll kDmaUnroll
             for (; h < hb; ++h, src += N, dst += W::SS) piece(src, dst);
         }
 #pragma unroll 1
@@ -578,11 +564,7 @@ template <int CTRL>
 __device__ __forceinline__ unsigned dpp_u32(unsigned v) {
     // (permutations: every lane has a source; no old value, so the move can
     // fold into its consumer)
-#ifdef LPHY_AB_DPP_OLD  // A/B timing only: the old-value form
-    return (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, 0xF, 0xF, false);
-#else
     return (unsigned)__builtin_amdgcn_mov_dpp((int)v, CTRL, 0xF, 0xF, true);
-#endif
 }
 __device__ __forceinline__ void top2_add(unsigned& K1, unsigned& K2, unsigned o1, unsigned o2) {
     K2 = med3_u32(K1, o1, K2 > o2 ? K2 : o2);
@@ -1188,11 +1170,11 @@ __device__ __forceinline__ void wsettle(KArgs ka, lds_cf32* lbuf, const lds_cf32
             for (int r = 0; r < W::PPS; r += 4) {
                 g_void* g = (g_void*)(src + s * N + 128 * r);
                 lds_void* ld = (lds_void*)(buf + (2 * j + s) * W::SS + 128 * r);
-                __builtin_amdgcn_global_load_lds(g, ld, 16, 0, LPHY_IQ_CPOL);
-                if constexpr (W::PPS >= 2) __builtin_amdgcn_global_load_lds(g, ld, 16, 1024, LPHY_IQ_CPOL);
+                __builtin_amdgcn_global_load_lds(g, ld, 16, 0, kIqCpol);
+                if constexpr (W::PPS >= 2) __builtin_amdgcn_global_load_lds(g, ld, 16, 1024, kIqCpol);
                 if constexpr (W::PPS >= 4) {
-                    __builtin_amdgcn_global_load_lds(g, ld, 16, 2048, LPHY_IQ_CPOL);
-                    __builtin_amdgcn_global_load_lds(g, ld, 16, 3072, LPHY_IQ_CPOL);
+                    __builtin_amdgcn_global_load_lds(g, ld, 16, 2048, kIqCpol);
+                    __builtin_amdgcn_global_load_lds(g, ld, 16, 3072, kIqCpol);
                 }
             }
         }
@@ -1551,10 +1533,7 @@ __global__ __launch_bounds__(256, 1) void k_wave(FrameArgs P) {
     // kPvBackoff), so input that never certifies this way (mode 0's IQ, whose
     // offsets put every tone between two bins; noise) pays one attempt per
     // 2^kPvBackoff frames instead of one per frame; a success resets m.
-#ifndef LPHY_PV_BACKOFF  // (-D0: an attempt on every frame, the round-5 rule; timing A/B)
-#define LPHY_PV_BACKOFF 6
-#endif
-    constexpr unsigned kPvBackoff = LPHY_PV_BACKOFF;
+    constexpr unsigned kPvBackoff = 6;  // (0: an attempt on every frame, the round-5 rule)
     unsigned pv_miss = 0, pv_wait = 0;
     auto pv_frame = [&]() __attribute__((always_inline)) {
         if (pv_wait != 0) {
@@ -1584,9 +1563,7 @@ __global__ __launch_bounds__(256, 1) void k_wave(FrameArgs P) {
         const unsigned k = sch.frame(cu), f = fglob(k);
         cf32 v[64];
         WPH(7);
-#ifndef LPHY_ABLATE_W_VMWAIT  // timing experiments only
         wait_vm0();  // this unit's IQ has landed
-#endif
         WPH(0);
         if (sch.kind(cu) == kWSym) {
             const WFrame R0 = rec(k);
@@ -1684,10 +1661,7 @@ __global__ __launch_bounds__(256, 1) void k_wave(FrameArgs P) {
             // software-pipelined in chunks of 8 samples: chunk q + 1's LDS reads
             // are issued before chunk q's arithmetic (sched barriers pin the
             // order; a single wave per SIMD has no other wave to hide them)
-#ifndef LPHY_W_STAGE_DEPTH
-#define LPHY_W_STAGE_DEPTH 1
-#endif
-            constexpr int SD = LPHY_W_STAGE_DEPTH, SB = SD + 1;  // chunks in flight, buffers
+            constexpr int SD = 1, SB = SD + 1;  // chunks in flight, buffers
             cf32 xq[SB][8], dq[SB][8];
             constexpr bool WS = WIN && !M0T;  // the window's product in the staging (M0T: in the table)
             float wq[SB][WS ? 8 : 1];
@@ -1699,11 +1673,7 @@ __global__ __launch_bounds__(256, 1) void k_wave(FrameArgs P) {
                 for (int i = 0; i < 8; ++i) {
                     const int e = 8 * q + i;
                     if constexpr (WS) ws[i] = wtab[l + LPS * e];
-#ifndef LPHY_ABLATE_W_STAGE  // timing experiments only
                     xs[i] = lds_ld(buf, rb + ((LPS * e) << 3));
-#else
-                    xs[i] = cf32{(float)e, (float)l};
-#endif
                     if constexpr (DECH) ds[i] = lds_ld(dnl, (int)((d0 + (unsigned)((LPS * e) << 3)) & (unsigned)(8 * N - 1)));
                     if constexpr (M0T) ds[i] = mt[l + LPS * e];
                     else if constexpr (M0) ds[i] = dnl[l + LPS * e];
@@ -1785,25 +1755,11 @@ __global__ __launch_bounds__(256, 1) void k_wave(FrameArgs P) {
                     for (int e = 0; e < 64; ++e) v[e] = cmul_fma(cmul_fma(v[e], Qr[e & 7]), Pr[e >> 3]);
                 }
                 wpass1<SF, true>(v, ctw(A.tw));
-#ifndef LPHY_ABLATE_W_EXCH  // timing experiments only
                 wexchange<SF>(v, buf, h, l);
-#endif
-#ifdef LPHY_W_LATE_DMA
-                // pass 2's first stage consumes the exchange reads as they land;
-                // then the buffer is free for the next unit's IQ
-                wpass2_s2<SF, true>(v, T, A.tw, l);
-                wait_lgkm0();
-                dma_unit(nx);
-                WPH(3);
-                wpass2_s10<SF, true>(v, T, A.tw, l);
-#else
                 wait_lgkm0();  // the exchange reads are done: the buffer is free
-#ifndef LPHY_ABLATE_W_DMA  // timing experiments only
                 dma_unit(nx);  // the next unit's IQ lands during pass 2
-#endif
                 WPH(3);
                 wpass2<SF, true>(v, T, A.tw, l);
-#endif
                 WPH(4);
                 // keyed top two over the half's bins l + LPS e (key: |X|^2 bits,
                 // low 6 bits the element; see team_argmax2_keyed_first)
