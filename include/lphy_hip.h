@@ -32,6 +32,8 @@
  *                          frames found in a capture, from those records
  *   lphy_hip_channelize    no reference function: a wideband capture to the
  *                          per-channel streams the calls above take
+ *   lphy_hip_channelize_raw  the same from a capture of int16 or 8-bit samples,
+ *                            as the radio wrote it (lphy_sample_format, below)
  *   lphy_hip_synthesize    no reference function: per-channel streams (those
  *                          lphy_hip_tx_ragged makes) to one wideband stream
  *   lphy_hip_decode_batch  lora_phy::decode / lora_decode on device symbols
@@ -519,6 +521,66 @@ int lphy_hip_channelize(lphy_hip_ctx* ctx, const float* d_in, const lphy_chan_pl
                         const float* d_taps, const float* d_rot, float* d_out, void* stream);
 int lphy_hip_channelize_host(lphy_hip_ctx* ctx, const float* h_in, const lphy_chan_plan* plan,
                              const float* h_taps, const float* h_rot, float* h_out);
+
+/* ------------------------------------------------------------------------
+ * The channeliser on a capture as the radio wrote it: interleaved I/Q in one
+ * of the formats below, so that the largest object of the chain crosses the
+ * host link and lies in device memory at 4 or 2 bytes a sample instead of 8.
+ *
+ * lphy_hip_channelize_raw gives, byte for byte, what lphy_hip_channelize gives
+ * with the same plan and tables on the float32 capture x' of the same length:
+ *     LPHY_FMT_SC16, LPHY_FMT_SC8:  x'.re = (float)I           x'.im = (float)Q
+ *     LPHY_FMT_CU8:                 x'.re = (float)I - 127.5f  x'.im = (float)Q - 127.5f
+ *     LPHY_FMT_CF32:                x' = the capture: the call is lphy_hip_channelize
+ *                                   itself, same alignment rule, same bytes
+ * Every one of these conversions is exact in float32, -32768, -128 and the
+ * half-integers of CU8 included, so the result stays a pure function of the
+ * inputs.  There is no scale argument: the caller folds 1/32768 (or 1/128,
+ * 1/127.5) into the taps.  The call is a plain converter too: with channels =
+ * taps = decim = rot_period = 1, taps = (g, 0) and rot = (1, 0), output m is
+ * exactly (g * x'.re, g * x'.im) of sample first + m, each one float32
+ * product (every other operation of the definition adds or subtracts a zero or
+ * multiplies by one; a power-of-two g does not round at all), so a
+ * single-channel capture at the channel's own rate enters the chain through
+ * this call as well.
+ *
+ * *plan is used as it is, all its counts in samples, and the limits are those
+ * of lphy_hip_channelize.  Returns, all before any device call, in
+ * lphy_hip_channelize's order with two changes: directly after the
+ * null-pointer rows (ctx, plan, d_taps, d_rot; d_in or d_out null with outputs
+ * > 0) a format that is none of the four gives -EINVAL; and the alignment row
+ * asks d_in for lphy_hip_sample_bytes(format) bytes (8, 4, 2, 2) and the other
+ * three pointers for 8.  Everything after that row is unchanged: reserved, the
+ * zero counts, the -ERANGE rows in their order; outputs == 0 then returns 0
+ * and launches nothing.
+ *
+ * The device form is asynchronous on `stream`: one launch, no device
+ * allocation, nothing read back, no workgroup waits on another and no atomic.
+ * It writes out[c*out_stride + m] for m < outputs alone and reads no byte
+ * outside the samples its outputs name.  The host form goes through the
+ * context's stream and staging like lphy_hip_channelize_host: it moves the
+ * samples first .. first + (outputs-1)*decim + taps alone, at
+ * lphy_hip_sample_bytes(format) each (1/2 or 1/4 of the float32 form's
+ * upload), and all of h_out both ways.
+ *
+ * Not provided: the transmit mirror (lphy_hip_synthesize to integer samples
+ * needs a rounding and saturation rule of its own), lphy_hip_demod_stream on
+ * integer files, big-endian or non-interleaved captures, 12-bit packed formats.
+ * --------------------------------------------------------------------- */
+enum lphy_sample_format {
+    LPHY_FMT_CF32 = 0,  /* float32 I, float32 Q: what lphy_hip_channelize takes      */
+    LPHY_FMT_SC16 = 1,  /* int16 I, int16 Q, little endian                           */
+    LPHY_FMT_SC8  = 2,  /* int8 I, int8 Q                                            */
+    LPHY_FMT_CU8  = 3   /* uint8 I, uint8 Q, offset binary: value = byte - 127.5     */
+};
+size_t lphy_hip_sample_bytes(int format);   /* 8, 4, 2, 2; 0 for anything else; host-only */
+
+int lphy_hip_channelize_raw(lphy_hip_ctx* ctx, const void* d_in, int format,
+                            const lphy_chan_plan* plan, const float* d_taps,
+                            const float* d_rot, float* d_out, void* stream);
+int lphy_hip_channelize_raw_host(lphy_hip_ctx* ctx, const void* h_in, int format,
+                                 const lphy_chan_plan* plan, const float* h_taps,
+                                 const float* h_rot, float* h_out);
 
 /* ------------------------------------------------------------------------
  * Synthesiser: one wideband stream from `channels` narrow-band streams, the

@@ -20,6 +20,16 @@
 // own accumulator pair, so a lane runs 2 * CG independent chains.  No chain is
 // split: that is what the definition requires.  No workgroup waits on another,
 // no atomic, vector stores only.
+//
+// The capture's format (lphy_hip_channelize_raw) is a template parameter.
+// LPHY_FMT_CF32 is the kernel above.  An integer capture is converted to
+// float32 where it is staged, (float) of the integer and for CU8 one
+// subtraction of 127.5f, all exact, and stored as float2 into the same padded
+// image, so the loop and its order of operations are the float path's and so
+// are the bits:
+//   LDS path: 16-byte loads of 4 (SC16) or 8 (8-bit) samples between a head
+//     and a tail of single samples (chan_stage_split);
+//   global path: the lane converts its own sample in the loop.
 #pragma once
 #include "lphy_args.h"
 #include "lphy_resample_plan.h"
@@ -34,15 +44,60 @@ struct ChanArgs {
     unsigned rot_base;  // rot_first % R
 };
 
-template <int CG, bool LDS>
-__global__ __launch_bounds__(kTile) void k_chan(const float2* __restrict__ in, const float2* __restrict__ taps,
-                                                const float2* __restrict__ rot, float2* __restrict__ out,
-                                                ChanArgs A) {
+// One sample of a capture in format FMT as it lies in memory, and its float32 value.
+template <int FMT>
+struct ChanFmt;
+template <>
+struct ChanFmt<LPHY_FMT_CF32> {
+    using sample = float2;
+    static __device__ __forceinline__ float2 value(float2 s) { return s; }
+};
+template <>
+struct ChanFmt<LPHY_FMT_SC16> {
+    using sample = short2;
+    static __device__ __forceinline__ float2 value(short2 s) { return make_float2((float)s.x, (float)s.y); }
+};
+template <>
+struct ChanFmt<LPHY_FMT_SC8> {
+    using sample = char2;
+    static __device__ __forceinline__ float2 value(char2 s) { return make_float2((float)s.x, (float)s.y); }
+};
+template <>
+struct ChanFmt<LPHY_FMT_CU8> {
+    using sample = uchar2;
+    static __device__ __forceinline__ float2 value(uchar2 s) {
+        return make_float2((float)s.x - 127.5f, (float)s.y - 127.5f);
+    }
+};
+
+template <int CG, bool LDS, int FMT>
+__global__ __launch_bounds__(kTile) void k_chan(const typename ChanFmt<FMT>::sample* __restrict__ in,
+                                                const float2* __restrict__ taps, const float2* __restrict__ rot,
+                                                float2* __restrict__ out, ChanArgs A) {
+    using Fmt = ChanFmt<FMT>;
     extern __shared__ float2 chan_lds[];
     const unsigned tid = threadIdx.x;
     const ChanSpan sp = chan_tile_span(A.first, A.D, A.T, A.outputs, blockIdx.x);
-    const float2* __restrict__ src = in + sp.begin;
-    if constexpr (LDS) {
+    const typename Fmt::sample* __restrict__ src = in + sp.begin;
+    if constexpr (LDS && FMT != LPHY_FMT_CF32) {
+        // sp.samples < 2^24 on this path
+        constexpr unsigned kPer = 16 / sizeof(typename Fmt::sample);
+        const ChanStage st = chan_stage_split((uintptr_t)src, (unsigned)sp.samples, sizeof(typename Fmt::sample));
+        if (tid < st.head) chan_lds[chan_lds_slot(tid)] = Fmt::value(src[tid]);
+        for (unsigned v = tid; v < st.vectors; v += kTile) {
+            const unsigned i = st.head + kPer * v;
+            const uint4 w = *reinterpret_cast<const uint4*>(src + i);  // kPer samples in one load
+            typename Fmt::sample s[kPer];
+            __builtin_memcpy(s, &w, 16);
+#pragma unroll
+            for (unsigned j = 0; j < kPer; ++j) chan_lds[chan_lds_slot(i + j)] = Fmt::value(s[j]);
+        }
+        if (tid < st.tail) {
+            const unsigned i = st.head + kPer * st.vectors + tid;
+            chan_lds[chan_lds_slot(i)] = Fmt::value(src[i]);
+        }
+        __syncthreads();
+    } else if constexpr (LDS) {
         // sp.samples < 2^24 on this path
         const unsigned n = (unsigned)sp.samples;
         const unsigned head = (unsigned)(((uintptr_t)src >> 3) & 1);  // samples in front of a 16-byte boundary
@@ -72,7 +127,7 @@ __global__ __launch_bounds__(kTile) void k_chan(const float2* __restrict__ in, c
         for (unsigned k = 0; k < A.T; ++k) {
             float2 x;
             if constexpr (LDS) x = chan_lds[chan_lds_slot(x0 + k)];
-            else x = src[(unsigned long long)tid * A.D + k];
+            else x = Fmt::value(src[(unsigned long long)tid * A.D + k]);
 #pragma unroll
             for (int j = 0; j < CG; ++j) {
                 const float2 g = tp[j][k];
@@ -95,30 +150,47 @@ __global__ __launch_bounds__(kTile) void k_chan(const float2* __restrict__ in, c
 }
 
 // The launch; the plan has passed chan_args and has outputs > 0.
-template <int CG>
-void chan_launch_group(bool lds, dim3 grid, size_t lds_bytes, hipStream_t st, const float2* in, const float2* taps,
-                       const float2* rot, float2* out, const ChanArgs& A) {
-    if (lds) hipLaunchKernelGGL((k_chan<CG, true>), grid, dim3(kTile), lds_bytes, st, in, taps, rot, out, A);
-    else hipLaunchKernelGGL((k_chan<CG, false>), grid, dim3(kTile), 0, st, in, taps, rot, out, A);
+template <int CG, int FMT>
+void chan_launch_group(bool lds, dim3 grid, size_t lds_bytes, hipStream_t st, const typename ChanFmt<FMT>::sample* in,
+                       const float2* taps, const float2* rot, float2* out, const ChanArgs& A) {
+    if (lds) hipLaunchKernelGGL((k_chan<CG, true, FMT>), grid, dim3(kTile), lds_bytes, st, in, taps, rot, out, A);
+    else hipLaunchKernelGGL((k_chan<CG, false, FMT>), grid, dim3(kTile), 0, st, in, taps, rot, out, A);
 }
 
-inline void resample_launch(const lphy_chan_plan& p, const float* d_in, const float* d_taps, const float* d_rot,
-                            float* d_out, hipStream_t st) {
+template <int FMT>
+void chan_launch_format(const lphy_chan_plan& p, const void* d_in, const float* d_taps, const float* d_rot,
+                        float* d_out, hipStream_t st) {
     const ChanArgs A{p.first, p.outputs, p.out_stride, p.channels, p.taps, p.decim, p.rot_period,
                      (unsigned)(p.rot_first % p.rot_period)};
     const bool lds = chan_lds_path(p.decim, p.taps);
     const size_t lds_bytes = lds ? (size_t)chan_lds_slots(p.decim, p.taps) * 8 : 0;
     const dim3 grid((unsigned)res_tiles(p.outputs));
-    const float2* in = reinterpret_cast<const float2*>(d_in);
+    const auto* in = static_cast<const typename ChanFmt<FMT>::sample*>(d_in);
     const float2* taps = reinterpret_cast<const float2*>(d_taps);
     const float2* rot = reinterpret_cast<const float2*>(d_rot);
     float2* out = reinterpret_cast<float2*>(d_out);
     switch (res_group(p.channels)) {
-        case 1: chan_launch_group<1>(lds, grid, lds_bytes, st, in, taps, rot, out, A); break;
-        case 2: chan_launch_group<2>(lds, grid, lds_bytes, st, in, taps, rot, out, A); break;
-        case 4: chan_launch_group<4>(lds, grid, lds_bytes, st, in, taps, rot, out, A); break;
-        default: chan_launch_group<8>(lds, grid, lds_bytes, st, in, taps, rot, out, A); break;
+        case 1: chan_launch_group<1, FMT>(lds, grid, lds_bytes, st, in, taps, rot, out, A); break;
+        case 2: chan_launch_group<2, FMT>(lds, grid, lds_bytes, st, in, taps, rot, out, A); break;
+        case 4: chan_launch_group<4, FMT>(lds, grid, lds_bytes, st, in, taps, rot, out, A); break;
+        default: chan_launch_group<8, FMT>(lds, grid, lds_bytes, st, in, taps, rot, out, A); break;
     }
+}
+
+// `format` is one of the four (chan_raw_aligned)
+inline void chan_launch(const lphy_chan_plan& p, const void* d_in, int format, const float* d_taps,
+                        const float* d_rot, float* d_out, hipStream_t st) {
+    switch (format) {
+        case LPHY_FMT_SC16: chan_launch_format<LPHY_FMT_SC16>(p, d_in, d_taps, d_rot, d_out, st); break;
+        case LPHY_FMT_SC8: chan_launch_format<LPHY_FMT_SC8>(p, d_in, d_taps, d_rot, d_out, st); break;
+        case LPHY_FMT_CU8: chan_launch_format<LPHY_FMT_CU8>(p, d_in, d_taps, d_rot, d_out, st); break;
+        default: chan_launch_format<LPHY_FMT_CF32>(p, d_in, d_taps, d_rot, d_out, st); break;
+    }
+}
+
+inline void resample_launch(const lphy_chan_plan& p, const float* d_in, const float* d_taps, const float* d_rot,
+                            float* d_out, hipStream_t st) {
+    chan_launch_format<LPHY_FMT_CF32>(p, d_in, d_taps, d_rot, d_out, st);
 }
 
 }  // namespace

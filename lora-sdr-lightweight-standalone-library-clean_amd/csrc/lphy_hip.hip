@@ -757,8 +757,35 @@ int resample_entry(int (*args)(bool, const Plan*, bool, bool, bool, bool), lphy_
     if (int rc = resample_check(args, c, d_in, p, d_taps, d_rot, d_out)) return rc > 0 ? 0 : rc;
     return resample_impl(c, d_in, *p, d_taps, d_rot, d_out, (hipStream_t)stream);
 }
+
+// lphy_hip_channelize_raw's argument check and launch, as resample_check and
+// resample_impl: chan_args with the format's row and its alignment row
+// (chan_raw_aligned), and the kernel of the format.
+int chan_raw_check(const lphy_hip_ctx* c, const void* in, int format, const lphy_chan_plan* p, const float* taps,
+                   const float* rot, const float* out) {
+    if (int rc = chan_args(c != nullptr, p, taps && rot, in != nullptr, out != nullptr,
+                           chan_raw_aligned(in, format, taps, rot, out)))
+        return rc;
+    return p->outputs == 0;
+}
+
+int chan_raw_impl(lphy_hip_ctx* c, const void* d_in, int format, const lphy_chan_plan& p, const float* d_taps,
+                  const float* d_rot, float* d_out, hipStream_t st) {
+    HIP_OK(hipSetDevice(c->device));
+    chan_launch(p, d_in, format, d_taps, d_rot, d_out, st);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
 }  // namespace
 }  // extern "C++"
+
+size_t lphy_hip_sample_bytes(int format) { return chan_sample_bytes(format); }
+
+int lphy_hip_channelize_raw(lphy_hip_ctx* c, const void* d_in, int format, const lphy_chan_plan* p,
+                            const float* d_taps, const float* d_rot, float* d_out, void* stream) {
+    if (int rc = chan_raw_check(c, d_in, format, p, d_taps, d_rot, d_out)) return rc > 0 ? 0 : rc;
+    return chan_raw_impl(c, d_in, format, *p, d_taps, d_rot, d_out, (hipStream_t)stream);
+}
 
 int lphy_hip_channelize(lphy_hip_ctx* c, const float* d_in, const lphy_chan_plan* p, const float* d_taps,
                         const float* d_rot, float* d_out, void* stream) {

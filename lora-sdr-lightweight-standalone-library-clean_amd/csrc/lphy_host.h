@@ -220,6 +220,22 @@ int lphy_hip_channelize_host(lphy_hip_ctx* c, const float* h_in, const lphy_chan
         resample_impl(c, hc.dev<float>(0), q, hc.dev<float>(1), hc.dev<float>(2), hc.dev<float>(3), hc.stream()));
 }
 
+// The same from a capture in `format`: the samples go up at the format's bytes each.
+int lphy_hip_channelize_raw_host(lphy_hip_ctx* c, const void* h_in, int format, const lphy_chan_plan* p,
+                                 const float* h_taps, const float* h_rot, float* h_out) {
+    if (int rc = chan_raw_check(c, h_in, format, p, h_taps, h_rot, h_out)) return rc > 0 ? 0 : rc;
+    const size_t bytes = chan_sample_bytes(format);
+    lphy_chan_plan q = *p;
+    q.in_samples = (p->outputs - 1) * p->decim + p->taps;
+    q.first = 0;
+    HostCall hc(c, kPageable);
+    if (int rc = hc.begin(chan_raw_plan(q.in_samples * bytes, p->channels, p->taps, p->rot_period, p->out_stride),
+                          {static_cast<const char*>(h_in) + p->first * bytes, h_taps, h_rot, h_out}))
+        return rc;
+    return hc.finish(chan_raw_impl(c, hc.dev<void>(0), format, q, hc.dev<float>(1), hc.dev<float>(2),
+                                   hc.dev<float>(3), hc.stream()));
+}
+
 // The synthesiser on host buffers: the channels' streams (from the first
 // channel's first sample to the last channel's last, strides included), the
 // two tables in, the one launch, `outputs` samples back.

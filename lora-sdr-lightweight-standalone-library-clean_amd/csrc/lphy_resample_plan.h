@@ -4,9 +4,12 @@
 // values: what the two share (the limits, the tile, the channel grouping and
 // the head of the argument check), then each one's output count, tile
 // geometry (which samples a workgroup stages, and where in its LDS), LDS-path
-// rule and argument check.  Plain C++ with LPHY_HD in front of what the kernels
-// call too, no HIP: the device forms, the host forms and the CPU tests
-// (tests/cpp/channelize_check.cpp, synthesize_check.cpp) share it.
+// rule and argument check, and for the channeliser on integer captures
+// (lphy_hip_channelize_raw) the sample sizes, the two rows it adds to the check
+// and the split of a span into 16-byte loads.  Plain C++ with LPHY_HD in front
+// of what the kernels call too, no HIP: the device forms, the host forms and
+// the CPU tests (tests/cpp/channelize_check.cpp, channelize_raw_check.cpp,
+// synthesize_check.cpp) share it.
 #pragma once
 #include <cerrno>
 #include <cstddef>
@@ -109,6 +112,46 @@ inline int chan_args(bool ctx, const lphy_chan_plan* p, bool tables, bool in, bo
         return -ERANGE;
     if (p->out_stride > kResMaxSamples / p->channels) return -ERANGE;
     return 0;
+}
+
+// ---- the channeliser on integer captures (lphy_hip_channelize_raw) ------------
+// lphy_hip_sample_bytes: one I/Q pair of `format`, 0 for no format
+LPHY_HD size_t chan_sample_bytes(int format) {
+    switch (format) {
+        case LPHY_FMT_CF32: return 8;
+        case LPHY_FMT_SC16: return 4;
+        case LPHY_FMT_SC8:
+        case LPHY_FMT_CU8: return 2;
+        default: return 0;
+    }
+}
+
+// The format's row and the alignment row of lphy_hip_channelize_raw, which
+// stand together directly behind the null-pointer rows and both give -EINVAL:
+// `format` is one of the four, `in` lies on a multiple of its sample's bytes
+// and the other three on 8.  chan_args takes the answer as its `aligned`; with
+// LPHY_FMT_CF32 it is res_aligned's.
+inline bool chan_raw_aligned(const void* in, int format, const void* taps, const void* rot, const void* out) {
+    const size_t b = chan_sample_bytes(format);
+    return b != 0 && ((uintptr_t)in & (b - 1)) == 0 && res_aligned(nullptr, taps, rot, out);
+}
+
+// How a workgroup stages the `n` samples of `bytes` each (4 or 2) that begin at
+// address `addr` (a multiple of `bytes`) with 16-byte loads: `head` single
+// samples up to the first 16-byte boundary, `vectors` loads of 16 / bytes
+// samples each, `tail` single samples.  Unlike the float path's head of at most
+// one sample, which a span of n >= 1 always holds, this head can be longer
+// than the span: then it is the whole span.  Sample i of the span is head
+// sample i, sample i - head - (16 / bytes) * vectors of the tail, or in vector
+// (i - head) / (16 / bytes).
+struct ChanStage {
+    uint32_t head, vectors, tail;
+};
+LPHY_HD ChanStage chan_stage_split(uintptr_t addr, uint32_t n, uint32_t bytes) {
+    const uint32_t per = 16 / bytes;
+    const uint32_t front = (uint32_t)((16 - (addr & 15)) & 15) / bytes;
+    const uint32_t head = n < front ? n : front;
+    return ChanStage{head, (n - head) / per, (n - head) % per};
 }
 
 // ---- the synthesiser ---------------------------------------------------------

@@ -167,12 +167,17 @@ inline StagePlan find_plan(size_t windows, size_t max_frames, size_t work_bytes)
 // the caller's values go in, so that the slots past `outputs` come back as they
 // went) - lphy_hip_channelize_host.  Like find_plan not among the plans
 // lphy_hip_ctx_reserve sizes for: a wideband capture is not a frame shape.
-inline StagePlan chan_plan(size_t samples, size_t channels, size_t taps, size_t rot_period, size_t out_stride) {
+// chan_raw_plan: the same for lphy_hip_channelize_raw_host, whose samples are
+// of the capture's format: `in_bytes` = samples * lphy_hip_sample_bytes.
+inline StagePlan chan_raw_plan(size_t in_bytes, size_t channels, size_t taps, size_t rot_period, size_t out_stride) {
     return StagePlan()
-        .add(samples * kIqBytes, kStageIn)
+        .add(in_bytes, kStageIn)
         .add(channels * taps * kIqBytes, kStageIn)
         .add(channels * rot_period * kIqBytes, kStageIn)
         .add(channels * out_stride * kIqBytes, kStageInOut);
+}
+inline StagePlan chan_plan(size_t samples, size_t channels, size_t taps, size_t rot_period, size_t out_stride) {
+    return chan_raw_plan(samples * kIqBytes, channels, taps, rot_period, out_stride);
 }
 
 // in (the channels' streams, first sample of the first to last sample of the

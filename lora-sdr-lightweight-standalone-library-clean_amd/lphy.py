@@ -133,6 +133,24 @@ def channelize_outputs(in_samples: int, first: int, taps: int, decim: int) -> in
     return int(load().lphy_hip_channelize_outputs(in_samples, first, taps, decim))
 
 
+# enum lphy_sample_format (include/lphy_hip.h): what a capture's I/Q pairs are made of
+FMT_CF32, FMT_SC16, FMT_SC8, FMT_CU8 = 0, 1, 2, 3
+_FMT_DTYPE = {FMT_CF32: np.dtype(np.float32), FMT_SC16: np.dtype("<i2"), FMT_SC8: np.dtype(np.int8),
+              FMT_CU8: np.dtype(np.uint8)}
+
+
+def sample_bytes(fmt: int) -> int:
+    """Bytes of one I/Q pair of format `fmt` (lphy_hip_sample_bytes): 8, 4, 2,
+    2; 0 for anything else."""
+    return int(load().lphy_hip_sample_bytes(fmt))
+
+
+def _fmt_dtype(fmt: int) -> np.dtype:
+    if fmt not in _FMT_DTYPE:
+        raise ValueError(f"fmt: one of FMT_CF32, FMT_SC16, FMT_SC8, FMT_CU8 expected, got {fmt!r}")
+    return _FMT_DTYPE[fmt]
+
+
 def _design_tables(who: str, centres, step: int, taps: int, cutoff: float, beta: float, synth: bool):
     """What chan_design and synth_design share: the Kaiser(beta)-windowed sinc
     with unit gain at DC, the exact (Fraction) phase reduction, the period R of
@@ -244,6 +262,7 @@ EXPORTS = (
     "lphy_hip_detect_ragged", "lphy_hip_detect_ragged_host",
     "lphy_hip_find_frames_workspace", "lphy_hip_find_frames", "lphy_hip_find_frames_host",
     "lphy_hip_channelize_outputs", "lphy_hip_channelize", "lphy_hip_channelize_host",
+    "lphy_hip_sample_bytes", "lphy_hip_channelize_raw", "lphy_hip_channelize_raw_host",
     "lphy_hip_synthesize_outputs", "lphy_hip_synthesize", "lphy_hip_synthesize_host",
     "lphy_hip_symbol_samples", "lphy_hip_lorawan_build_ragged", "lphy_hip_lorawan_tx_layout",
     "lphy_hip_lorawan_parse_ragged", "lphy_hip_lorawan_sessions_check",
@@ -318,6 +337,10 @@ def load(path: Path | None = None) -> C.CDLL:
     L.lphy_hip_channelize_outputs.restype = C.c_uint64
     L.lphy_hip_channelize.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp]
     L.lphy_hip_channelize_host.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp]
+    L.lphy_hip_sample_bytes.argtypes = [C.c_int]
+    L.lphy_hip_sample_bytes.restype = _sz
+    L.lphy_hip_channelize_raw.argtypes = [_vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]
+    L.lphy_hip_channelize_raw_host.argtypes = [_vp, _vp, C.c_int, _vp, _vp, _vp, _vp]
     L.lphy_hip_synthesize_outputs.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32]
     L.lphy_hip_synthesize_outputs.restype = C.c_uint64
     L.lphy_hip_synthesize.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp]
@@ -689,22 +712,68 @@ class Demodulator:
         leaves alone.  Returns the (channels, outputs) complex64 result (a view
         of `out` when given)."""
         x = np.ascontiguousarray(iq, np.complex64).reshape(-1)
+        return self._channelize_host(x, x.size, None, taps, rot, decim, first, outputs, rot_first, out)
+
+    def _channelize_host(self, x, n, fmt, taps, rot, decim, first, outputs, rot_first, out):
+        """channelize_host and channelize_raw_host behind their own check of the
+        capture: `x` flat and contiguous, `n` its samples, `fmt` None for the
+        float32 entry point."""
         t = np.ascontiguousarray(taps, np.complex64)
         r = np.ascontiguousarray(rot, np.complex64)
         if t.ndim != 2 or r.ndim != 2 or t.shape[0] != r.shape[0]:
             raise ValueError(f"taps {t.shape} and rot {r.shape}: [channels, T] and [channels, R] expected")
         if outputs is None:
-            outputs = channelize_outputs(x.size, first, t.shape[1], decim)
+            outputs = channelize_outputs(n, first, t.shape[1], decim)
         if out is None:
             out = np.zeros((t.shape[0], outputs), np.complex64)
         if (out.dtype != np.complex64 or out.ndim != 2 or not out.flags.c_contiguous or out.shape[0] != t.shape[0]
                 or out.shape[1] < outputs):
             raise ValueError(f"out: C-contiguous complex64 [{t.shape[0]}, >= {outputs}] expected")
-        p = chan_plan(first, x.size, outputs, out.shape[1], rot_first, t.shape[0], t.shape[1], decim, r.shape[1])
+        p = chan_plan(first, n, outputs, out.shape[1], rot_first, t.shape[0], t.shape[1], decim, r.shape[1])
         p_x, p_t, p_r, p_out = _host_ptrs(x, t, r, out)
-        _chk(self.lib.lphy_hip_channelize_host(self.ctx, p_x, p.ctypes.data, p_t, p_r, p_out),
-             "lphy_hip_channelize_host")
+        if fmt is None:
+            _chk(self.lib.lphy_hip_channelize_host(self.ctx, p_x, p.ctypes.data, p_t, p_r, p_out),
+                 "lphy_hip_channelize_host")
+        else:
+            _chk(self.lib.lphy_hip_channelize_raw_host(self.ctx, p_x, fmt, p.ctypes.data, p_t, p_r, p_out),
+                 "lphy_hip_channelize_raw_host")
         return out[:, :outputs]
+
+    def channelize_raw(self, iq, fmt, plan, taps, rot, out, stream=None):
+        """channelize() on a capture as the radio wrote it
+        (lphy_hip_channelize_raw): `iq` is a device tensor of 2 * in_samples
+        elements of fmt's type - float32 (FMT_CF32), int16 (FMT_SC16), int8
+        (FMT_SC8) or uint8 (FMT_CU8, value = byte - 127.5) - interleaved I, Q.
+        The result is channelize()'s on the capture converted to float32, which
+        is exact; there is no scale: fold 1/32768 (1/128) into `taps`.
+        Everything else as channelize().  Asynchronous."""
+        dv = self.device
+        dt = _fmt_dtype(fmt)
+        p, q = _one_plan(plan, CHAN_PLAN, "CHAN_PLAN")
+        p_in = _dev_buf(iq, "iq", dv, 0, None)
+        want = "torch." + dt.name  # torch's dtypes print as numpy names them
+        if str(iq.dtype) != want or iq.numel() != 2 * int(q["in_samples"]):
+            raise ValueError(f"iq: {2 * int(q['in_samples'])} elements of {want} expected, got {iq.numel()} of "
+                             f"{iq.dtype}")
+        p_taps, p_rot = _tables_bufs(taps, rot, dv, q)
+        p_out = _dev_buf(out, "out", dv, int(q["channels"]) * int(q["out_stride"]) * 8, None)
+        _chk(self.lib.lphy_hip_channelize_raw(self.ctx, p_in, fmt, p.ctypes.data, p_taps, p_rot, p_out, stream),
+             "lphy_hip_channelize_raw")
+
+    def channelize_raw_host(self, x: np.ndarray, fmt: int, taps: np.ndarray, rot: np.ndarray, decim: int,
+                            first: int = 0, outputs: int | None = None, rot_first: int = 0,
+                            out: np.ndarray | None = None) -> np.ndarray:
+        """channelize_host() on a capture as the radio wrote it
+        (lphy_hip_channelize_raw_host): `x` is a numpy array of fmt's dtype,
+        shaped [n, 2] (I, Q) or flat with 2n elements; the samples go to the
+        device at sample_bytes(fmt) each.  Everything else as
+        channelize_host()."""
+        dt = _fmt_dtype(fmt)
+        x = np.asarray(x)
+        if x.dtype != dt or not (x.ndim == 1 and x.size % 2 == 0 or x.ndim == 2 and x.shape[1] == 2):
+            raise ValueError(f"x: {dt.name} [n, 2] or flat with 2n elements expected, got {x.dtype} {x.shape}")
+        x = np.ascontiguousarray(x).reshape(-1)
+        return self._channelize_host(x, x.size // 2, fmt, taps, rot, decim, first, outputs, rot_first, out)
 
     # --- the synthesiser (lphy_hip_synthesize*) --------------------------
     def synthesize(self, streams, plan, taps, rot, out, stream=None):
