@@ -950,7 +950,8 @@ const char* lphy_hip_version(void);
 
 /* Symbols the fused kernel recomputed with the exact per-sample rotation
  * because the certified fast path could not prove its argmax (near-ties,
- * NaN, shifted windows; every symbol under LPHY_F_EXACT_ROTATION), summed
+ * NaN, shifted windows; every symbol under LPHY_F_EXACT_ROTATION; every
+ * symbol, sync symbols included, of a frame re-run whole), summed
  * over launches on `ctx`'s device since the last reset.  Diagnostic only:
  * synchronises the device.  Returns 0 or -EIO. */
 int lphy_hip_recheck_count(lphy_hip_ctx* ctx, unsigned long long* out, int reset);

@@ -373,6 +373,8 @@ __global__ __launch_bounds__(kTile) void k_post(DemodArgs A, FinalArgs F, int fi
             __syncthreads();
             const unsigned n = fcount;
             for (unsigned k = 0; k < n; ++k) exact_frame<SF, MODE>(A, flist[k], sh);
+            // every symbol of these frames was re-run exactly (lphy_hip_recheck_count)
+            if (threadIdx.x == 0) atomicAdd(&A.counters[kCtrRecheck], (unsigned long long)n * A.total_syms);
         }
         if (__syncthreads_or(recheck)) {
             recheck_frames<SF, MODE>(A, (unsigned long long)blockIdx.x * kTile, recheck, sh);

@@ -23,33 +23,8 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 
-def _bits(x):
-    return np.asarray(x, np.float32).view(np.uint32)
-
-
-def _two_tone_frames(oracle, sf, nf, seed):
-    rng = np.random.default_rng(seed)
-    N = 1 << sf
-    S = 64
-    ks = np.unique(np.round(2.0 ** np.linspace(0, 10, S)).astype(np.int64))
-    frames = []
-    for f in range(nf):
-        a = rng.integers(0, 256, S).astype(np.uint16) % N
-        b = (a + rng.integers(1, N, S)).astype(np.uint16) % N
-        xa = oracle.modulate(a, sf).astype(np.complex128)
-        xb = oracle.modulate(b, sf).astype(np.complex128)
-        # per-symbol amplitude ratio 1 + k 2^-23 (tone b larger or smaller)
-        k = ks[(np.arange(S) + f) % ks.size]
-        r = 1.0 + k * 2.0 ** -23
-        gain_b = np.ones(xa.size)
-        for s in range(S):
-            gain_b[(s + 2) * N:(s + 3) * N] = r[s] if (s + f) % 2 else 1.0 / r[s]
-        x = xa + xb * gain_b
-        t = np.arange(x.size)
-        x = x * np.exp(2j * np.pi * rng.uniform(-0.4, 0.4) / N * t) * [0.7, 1.0, 1.9][f % 3]
-        x = np.roll(x, int(rng.integers(-N // 4, N // 4 + 1)))
-        frames.append(x.astype(np.complex64))
-    return np.stack(frames)
+from demod_frames import (assert_straddle as _assert_straddle, bits as _bits,  # noqa: E402
+                          two_tone_frames as _two_tone_frames)
 
 
 @pytest.mark.parametrize("sf,nf", [(7, 48), (8, 24), (9, 20), (11, 6), (12, 4)])
@@ -161,22 +136,6 @@ def test_frames_kernel_threshold_straddled(oracle, lphy, sf):
         assert _bits(meta["time_offset"][0]) == _bits(omet[1]), ctx
         rows.append((k, n_exact))
     _assert_straddle(rows, nsym, thr)
-
-
-def _assert_straddle(rows, nsym, thr):
-    """Frames below the predicted threshold re-run every data symbol,
-    frames above it none, the switch within a factor 2 of the prediction."""
-    msg = "\n".join(f"r-1 {k:.4g}: exact {n}" for k, n in rows) + f"\npredicted r-1 {thr:.4g}"
-    assert all(0 <= n <= nsym for _, n in rows), msg
-    near = [(k, n) for k, n in rows if k < 16 * thr]
-    certified = sum(nsym - n for _, n in near)
-    rerun = sum(n for _, n in near)
-    assert certified > 0 and rerun > 0, msg
-    all_rerun = [k for k, n in rows if n == nsym]
-    none_rerun = [k for k, n in rows if n == 0]
-    assert all_rerun and none_rerun, msg
-    assert max(all_rerun) < min(none_rerun) < 16 * thr, msg
-    assert thr / 2 < max(all_rerun) and min(none_rerun) < 2 * thr, msg
 
 
 @pytest.mark.parametrize("sf", [7, 8])

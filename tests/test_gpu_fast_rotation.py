@@ -15,39 +15,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 
-def _impaired(oracle, sf, nf, seed, plen=32, snr_db=None, cfo_bins=0.4, gain=(1.0,),
-              max_delay=0):
-    rng = np.random.default_rng(seed)
-    N = 1 << sf
-    frames = []
-    for f in range(nf):
-        p = rng.integers(0, 256, plen, dtype=np.uint8).tobytes()
-        x = oracle.modulate(oracle.encode(p), sf).astype(np.complex128)
-        t = np.arange(x.size)
-        x = x * np.exp(2j * np.pi * rng.uniform(-cfo_bins, cfo_bins) / N * t)
-        if max_delay:
-            x = np.roll(x, int(rng.integers(-max_delay, max_delay + 1)))
-        if snr_db is not None:
-            s = np.sqrt(10 ** (-snr_db / 10) / 2)
-            x = x + s * (rng.standard_normal(x.size) + 1j * rng.standard_normal(x.size))
-        frames.append((x * gain[f % len(gain)]).astype(np.complex64))
-    return np.stack(frames)
-
-
-def _both(lphy, d, iq, mode):
-    """The product library's run and the exact rotation's (test build:
-    LPHY_F_EXACT_ROTATION is not in the product library)."""
-    nf, fs = iq.shape
-    a = d.demod_host(iq, nf, fs, mode, lphy.F_DECODE)
-    n_fast = d.recheck_count(reset=True)
-    dt = lphy.Demodulator(d.sf, d.bw_hz, d.osr, d.window, test_build=True)
-    b = dt.demod_host(iq, nf, fs, mode, lphy.F_DECODE | lphy.F_EXACT_ROTATION)
-    n_exact = dt.recheck_count(reset=True)
-    assert dt.bounds_violations() == 0
-    np.testing.assert_array_equal(a[0], b[0])
-    np.testing.assert_array_equal(a[1], b[1])
-    np.testing.assert_array_equal(a[2].view(np.uint8), b[2].view(np.uint8))
-    return a, n_fast, n_exact
+from demod_frames import fast_and_exact as _both, impaired_frames as _impaired  # noqa: E402
 
 
 MODES = [0, 1, 2]

@@ -45,7 +45,8 @@ def _nan_bits_equal(a, b):
 # max-abs over team pairs of 4 and 32 lanes (NaN / inf there must reach the
 # exact re-run as the 2-symbol scan made them)
 @pytest.mark.parametrize("sf,osr", [(7, 1), (9, 1), (11, 1), (8, 2), (5, 1), (8, 1)])
-@pytest.mark.parametrize("flags", [0, 32, 64])  # 32 = F_DECODE, 64 = F_EXACT_ROTATION
+# (every row decodes: LPHY_F_DECODE is added to each call below)
+@pytest.mark.parametrize("flags", [0, 32, 64])  # 32 = F_UNFUSED, 64 = F_EXACT_ROTATION
 def test_nonfinite_frames_all_modes(oracle, lphy, sf, osr, flags):
     iq = _frames(oracle, sf, osr, 6, seed=sf * 10 + osr)
     nf, fs = iq.shape

@@ -28,36 +28,8 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 
-def _bits(x):
-    return np.asarray(x, np.float32).view(np.uint32)
-
-
-def _tones_frame(oracle, sf, gains, seed, cfo=0.2, roll=True):
-    """One frame whose every data symbol is len(gains) tones (distinct
-    random bins) with relative amplitudes `gains` (a callable of the symbol
-    index giving the list), under a small CFO and delay."""
-    rng = np.random.default_rng(seed)
-    N = 1 << sf
-    S = 64
-    base = rng.integers(0, N, S)
-    x = None
-    g0 = gains(0)
-    for t in range(len(g0)):
-        # side tone t in its own part of the spectrum (never on another tone)
-        off = 0 if t == 0 else int(rng.integers((2 * t - 1) * N // 8, 2 * t * N // 8 + 1))
-        syms = ((base + off) % N).astype(np.uint16)
-        xt = oracle.modulate(syms, sf).astype(np.complex128)
-        g = np.ones(xt.size)
-        for s in range(S):
-            g[(s + 2) * N:(s + 3) * N] = gains(s)[t]
-        if t > 0:
-            g[:2 * N] = 0.0  # the sync symbols: one tone
-        x = xt * g if x is None else x + xt * g
-    n = np.arange(x.size)
-    x = x * np.exp(2j * np.pi * rng.uniform(-cfo, cfo) / N * n)
-    if roll:
-        x = np.roll(x, int(rng.integers(-N // 8, N // 8 + 1)))
-    return x.astype(np.complex64)
+from demod_frames import (bits as _bits, pure_tone_frame as _pure_tone_frame,  # noqa: E402
+                          tones_frame as _tones_frame)
 
 
 def _check_one(oracle, sf, x, mode, syms, meta, ctx):
@@ -82,29 +54,6 @@ def _product_one(oracle, dp, sf, x, mode, ctx):
     n = dp.recheck_count(reset=True)
     _check_one(oracle, sf, x, mode, syms, meta, ctx)
     return n
-
-
-def _pure_tone_frame(sf, amps, gains, seed, nsym=64):
-    """Mode-1 input (dechirped samples) built directly: two sync symbols of
-    one tone each, then data symbols of len(amps) pure integer tones at
-    distinct random bins, tone t of symbol s with amplitude amps[t] *
-    gains(s)[t].  No wrap-around phase step (a modulated chirp's dechirp
-    has one, which leaks energy out of the peak and breaks an amplitude
-    tie), so the peaks are the amplitudes times N."""
-    rng = np.random.default_rng(seed)
-    N = 1 << sf
-    n = np.arange(N)
-    tone = lambda k: np.exp(2j * np.pi * k * n / N)
-    # both sync symbols at bin 0: the estimate (LoRaDemod.cpp:80-136) then
-    # finds cfo 0 and time offset 0, so the data tones stay on integer bins
-    # (a fractional rotation would leak each tone into the others' bins and
-    # break a tie by far more than the sweeps' ratios)
-    out = [tone(0), tone(0)]
-    for s in range(nsym):
-        bins = rng.choice(N, len(amps), replace=False)
-        g = gains(s)
-        out.append(sum(amps[t] * g[t] * tone(int(bins[t])) for t in range(len(amps))))
-    return np.concatenate(out).astype(np.complex64)
 
 
 @pytest.mark.parametrize("sf", [7, 8, 9, 10, 11, 12])
